@@ -16,7 +16,14 @@ on its own and reported under "allgather"; BASELINE config C4 (grouped_matmul, 5
 in-place RCCL all-gather) is the "c4" object with `compute_only` and `incl_allgather` side by side.
 (``--scaling weak`` grows the job with N instead: debugging only.)
 
-The JSON line also carries
+A plain run sets up, warms up, times --steps steps and prints the JSON line with the headline figure (`value`,
+`ms_per_step` = wall time of one timed step, ...) and nothing else.  ``--dump-outputs DIR`` writes what the last timed
+step returned: ``DIR/out.npy`` (``out_rank<r>.npy`` per rank when N > 1), float32, the rows of a fixed seeded sample of
+65 536 rows plus the first and last row of every relation (32 MiB at the full size), in ascending row order; the inputs
+are seeded, so two builds can be compared output for output.
+
+With ``--full`` the JSON line also carries
+  allgather     (N > 1) the RCCL all-gather of the sharded outputs, timed on its own
   roofline      dominant kernel vs the HBM roofline: algorithmic bytes / HIP-event kernel time on the launch stream
                 (pyg_hip_profile_*), plus `achievable`: what hand-written device copies of the same 1 read : 1 write
                 byte mix reach on this box on the same two buffers (pyg_hip_stream_copy: fine-grained sweep = the best
@@ -38,6 +45,7 @@ import argparse
 import ctypes
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -164,6 +172,24 @@ def stream_copy_rates(L, x, reps=5):
     return rates, ok
 
 
+DUMP_SAMPLE_ROWS = 1 << 16
+
+
+def dump_outputs(out_dir, out, ptr, rank, world):
+    """Writes the rows of `out` (this rank's output of the last timed step) at a fixed seeded sample of row indices plus
+    the first and last row of every non-empty relation, in ascending row order, as float32 (exact for bf16 and fp32)."""
+    n = out.size(0)
+    rng = np.random.default_rng(20_111_007)
+    rows = rng.choice(n, size=min(n, DUMP_SAMPLE_ROWS), replace=False)
+    p = ptr.cpu().numpy()
+    nonempty = p[1:] > p[:-1]
+    rows = np.unique(np.concatenate([rows, p[:-1][nonempty], p[1:][nonempty] - 1])).astype(np.int64)
+    sample = out.index_select(0, torch.from_numpy(rows).to(out.device)).float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    name = 'out' if world == 1 else f'out_rank{rank}'
+    np.save(os.path.join(out_dir, name + '.npy'), sample)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -179,14 +205,23 @@ def main():
                     help='tile schedule of the bf16 kernel (PYG_HIP_MM_SCHED_* of pyg_hip.h)')
     ap.add_argument('--debug-one-device', action='store_true',
                     help='debug only: all ranks share cuda:0 over gloo (exercises the N>1 code path on a 1-GPU box)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline figure: roofline and copy yardstick, all-gather, '
+                         'the other configs and ops (bench_legs.py), the sampler, the CPU baselines '
+                         '(--no-legs / --no-sampler / --no-cpu-baseline leave parts out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write a fixed sample of the last timed step\'s output to DIR/*.npy (float32)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
-        # `python bench.py --gpus N` without a launcher: become N ranks, one per GPU (what the driver's own
-        # `python -m torch.distributed.run ... bench.py --gpus N` command does)
-        have = torch.cuda.device_count()
-        if not args.debug_one_device and have < args.gpus:
-            sys.exit(f'bench.py: --gpus {args.gpus} asked for, but only {have} HIP device(s) are visible')
+        # `python bench.py --gpus N` without a launcher: N ranks, one per GPU, in a child launcher (what the driver's
+        # own `python -m torch.distributed.run ... bench.py --gpus N` command does)
+        if not args.debug_one_device:
+            have = torch.cuda.device_count()
+            if have < args.gpus:
+                sys.exit(f'bench.py: --gpus {args.gpus} asked for, but only {have} HIP device(s) are visible')
         import socket
         with socket.socket() as sock:
             sock.bind(('127.0.0.1', 0))
@@ -195,7 +230,8 @@ def main():
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}',
                '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execvpe(sys.executable, cmd, env)
+        rc = subprocess.call(cmd, env=env)
+        sys.exit(rc if rc >= 0 else 128 - rc)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -240,7 +276,8 @@ def main():
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
-    L.pyg_hip_profile_enable(1)
+    if args.full:   # HIP events around the dominant kernel of every timed launch (roofline)
+        L.pyg_hip_profile_enable(1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step()
@@ -249,11 +286,12 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    buf = (ctypes.c_float * max(args.steps, 1))()
-    nk = L.pyg_hip_profile_collect(buf, args.steps)
-    L.pyg_hip_profile_enable(0)
-    kernel_ms = float(np.mean([buf[i] for i in range(min(nk, args.steps))])) if nk else float('nan')
-    variant = ops.matmul_last_variant()
+    if args.full:
+        buf = (ctypes.c_float * max(args.steps, 1))()
+        nk = L.pyg_hip_profile_collect(buf, args.steps)
+        L.pyg_hip_profile_enable(0)
+        kernel_ms = float(np.mean([buf[i] for i in range(min(nk, args.steps))])) if nk else float('nan')
+        variant = ops.matmul_last_variant()
 
     t = torch.tensor([elapsed], device=device, dtype=torch.float64)
     if distributed:
@@ -262,6 +300,30 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     flops = 2.0 * N * F * F
     value = flops / (elapsed / args.steps) / 1e9
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, ptr, rank, world)
+
+    result = None
+    if rank == 0:
+        result = {
+            'metric': 'segment_matmul GFLOP/s + sampled-edges/sec, 1/2/4/8 MI355X vs CPU ref',
+            'value': round(value, 1), 'unit': 'GFLOP/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True,
+            'scaling': args.scaling, 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
+            'config': {'workload': 'segment_matmul ogbn-mag-shaped: 154 relations, 21,111,007 rows, '
+                                   'F_in=F_out=128 (BASELINE.json configs[1])',
+                       'relations': B, 'rows': N, 'rows_per_gpu': N // world, 'F': F, 'scale': args.scale,
+                       'sharding': f'contiguous row shards x{world}, outputs left sharded (compute only)'},
+        }
+    if not args.full:
+        if rank == 0:
+            result['cpu_baseline'] = None
+            print(json.dumps(result), flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # dominant kernel vs HBM roofline (this rank's shard): algorithmic bytes per launch
     n_local = x.size(0)
@@ -333,19 +395,8 @@ def main():
         except Exception as e:  # noqa: BLE001 - the headline line must survive a collective failure
             allgather = dict(error=repr(e)[:200])
 
-    result = None
     if rank == 0:
-        result = {
-            'metric': 'segment_matmul GFLOP/s + sampled-edges/sec, 1/2/4/8 MI355X vs CPU ref',
-            'value': round(value, 1), 'unit': 'GFLOP/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True,
-            'scaling': args.scaling, 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
-            'config': {'workload': 'segment_matmul ogbn-mag-shaped: 154 relations, 21,111,007 rows, '
-                                   'F_in=F_out=128 (BASELINE.json configs[1])',
-                       'relations': B, 'rows': N, 'rows_per_gpu': N // world, 'F': F, 'scale': args.scale,
-                       'sharding': f'contiguous row shards x{world}, outputs left sharded (compute only)'},
-            'roofline': roofline,
-        }
+        result['roofline'] = roofline
         if allgather is not None:
             result['allgather'] = allgather
 

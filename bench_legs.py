@@ -2,8 +2,8 @@
 algorithmic bytes (SURVEY.md 8(d) formulas), the measured time per call (HIP events on the launch stream, inputs
 resident in HBM) and the fraction of the 8 TB/s HBM peak that makes.  Rank 0 / one GPU unless stated otherwise.
 
-Every leg is bounded (a few launches of a fixed synthetic workload) so that the default `python bench.py` run still
-finishes within a few minutes.
+The legs run with `python bench.py --full` only.  Every leg is bounded (a few launches of a fixed synthetic workload) so
+that such a run still finishes within a few minutes.
 """
 import math
 import time

@@ -1,13 +1,9 @@
-"""Loader of tests/golden/biased_golden.npz (written by make_biased_golden.py with the real torch ops)."""
-import os.path as osp
-
-import numpy as np
-
-HERE = osp.dirname(osp.abspath(__file__))
+"""Loader of tests/golden/biased_golden.part*.npz (written by make_biased_golden.py with the real torch ops)."""
+from tests.golden import parts
 
 
 def load():
-    z = np.load(osp.join(HERE, 'biased_golden.npz'))
+    z = parts.load('biased_golden')
     cases = []
     for c in range(int(z['num_cases'][0])):
         pre = f'c{c}_'

@@ -1,4 +1,4 @@
-"""Generates tests/golden/biased_golden.npz: biased (edge_weight) neighbour sampling computed with the REAL
+"""Generates tests/golden/biased_golden.part*.npz: biased (edge_weight) neighbour sampling computed with the REAL
 libtorch CPU ops the reference calls -- pyg_lib/csrc/sampler/cpu/neighbor_kernel.cpp:245-285:
 
     rand  = at::empty_like(weight).uniform_()         # global CPU generator
@@ -23,6 +23,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+import parts  # noqa: E402  tests/golden/parts.py, next to this script
 I64_MIN, I64_MAX = -2**63, 2**63 - 1
 
 
@@ -235,7 +236,7 @@ def main():
                         out[pre + f'nhops_{t}'] = np.array(ref[4][t], dtype=np.int64)
                     cid += 1
     out['num_cases'] = np.array([cid])
-    np.savez_compressed(os.path.join(HERE, 'biased_golden.npz'), **out)
+    parts.save('biased_golden', out)
     print(f'{cid} cases, {n_rows} sampled edges, oracle mismatches: {n_mismatch}')
 
 

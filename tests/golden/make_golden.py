@@ -5,7 +5,7 @@
 * mt19937_words.npz  -- words torch's CPU generator yields for the exact calls the reference's
   RandintEngine makes (pyg_lib/csrc/random/cpu/rand_engine.h:79-91): at::randint(INT64_MIN,
   INT64_MAX, [128]) once, then in-place Tensor.random_(INT64_MIN, INT64_MAX) refills.
-* matmul_golden.npz  -- segment_matmul / grouped_matmul expectations computed the way the
+* matmul_golden.part*.npz  -- segment_matmul / grouped_matmul expectations computed the way the
   reference's tests do (test/ops/test_matmul.py:14-45,48-93: per-segment `inputs[a:b] @ other[i]`
   with torch on CPU), for BASELINE config C1 (fp32), the docstring example, and ragged bf16
   segments including empty ones.  bf16 tensors are stored as uint16 bit patterns.
@@ -14,6 +14,8 @@ import os.path as osp
 
 import numpy as np
 import torch
+
+import parts  # tests/golden/parts.py, next to this script
 
 HERE = osp.dirname(osp.abspath(__file__))
 I64_MIN, I64_MAX = -2**63, 2**63 - 1
@@ -83,7 +85,7 @@ def matmul():
     oth = [torch.randn(16, 48), torch.randn(9, 42), torch.randn(32, 64)]
     for i, (a, o) in enumerate(zip(ins, oth)):
         d[f'g_in{i}'], d[f'g_ot{i}'], d[f'g_out{i}'] = a.numpy(), o.numpy(), (a @ o).numpy()
-    np.savez_compressed(osp.join(HERE, 'matmul_golden.npz'), **d)
+    parts.save('matmul_golden', d)
 
 
 if __name__ == '__main__':

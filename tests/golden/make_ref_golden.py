@@ -1,4 +1,4 @@
-"""Generates tests/golden/reduce_golden.npz with the REAL reference (build container only).
+"""Generates tests/golden/reduce_golden.part*.npz with the REAL reference (build container only).
 
     bash oracle/build_ref.sh && python tests/golden/make_ref_golden.py
 
@@ -11,6 +11,8 @@ import os.path as osp
 
 import numpy as np
 import torch
+
+import parts  # tests/golden/parts.py, next to this script
 
 HERE = osp.dirname(osp.abspath(__file__))
 ROOT = osp.dirname(osp.dirname(HERE))
@@ -178,5 +180,5 @@ if __name__ == '__main__':
     coo_cases()
     sort_cases()
     D['__cases__'] = np.array(META)
-    np.savez_compressed(osp.join(HERE, 'reduce_golden.npz'), **D)
-    print(f'{len(META)} cases ->', osp.join(HERE, 'reduce_golden.npz'))
+    parts.save('reduce_golden', D)
+    print(f'{len(META)} cases ->', osp.join(HERE, 'reduce_golden.part*.npz'))

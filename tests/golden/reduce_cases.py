@@ -1,8 +1,6 @@
-"""Reader for tests/golden/reduce_golden.npz (outputs of the REAL reference CPU kernels, recorded
+"""Reader for tests/golden/reduce_golden.part*.npz (outputs of the REAL reference CPU kernels, recorded
 by tests/golden/make_ref_golden.py through oracle/_ref)."""
-import os.path as osp
-
-import numpy as np
+from tests.golden import parts
 
 _D = None
 
@@ -10,7 +8,7 @@ _D = None
 def data():
     global _D
     if _D is None:
-        _D = np.load(osp.join(osp.dirname(osp.abspath(__file__)), 'reduce_golden.npz'))
+        _D = parts.load('reduce_golden')
     return _D
 
 

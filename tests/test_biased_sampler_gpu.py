@@ -1,5 +1,5 @@
 """Biased (edge_weight) neighbour sampling on the device: exact parity with the vectors computed with the real
-libtorch ops (tests/golden/biased_golden.npz), with the reference's own biased tests
+libtorch ops (tests/golden/biased_golden.part*.npz), with the reference's own biased tests
 (test/csrc/sampler/test_neighbor.cpp:300-377) and with the oracle on larger graphs, including rows whose keys
 tie (zero weights, equal weights) -- those follow libstdc++'s partial_sort / nth_element order."""
 import ctypes

@@ -188,7 +188,7 @@ def test_index_sort_on_cpu(dtype):
 
 # ---- scatter / segment_coo / gather_coo / segment_csr / gather_csr / softmax_csr on CPU tensors ----------------------
 # (key CPU; csrc/binding/cpu_reduce.h).  The expectations are the outputs recorded from the REAL reference build
-# (tests/golden/reduce_golden.npz, csr_golden.npz; oracle/build_ref.sh): the CPU kernels keep the reference's order of
+# (tests/golden/reduce_golden.part*.npz, csr_golden.npz; oracle/build_ref.sh): the CPU kernels keep the reference's order of
 # operations, so everything -- floating sums and bf16 per-element rounding included -- must match bit for bit.
 
 from tests.golden import reduce_cases as RC  # noqa: E402

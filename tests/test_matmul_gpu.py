@@ -4,8 +4,6 @@ Modelled on the reference's test/ops/test_matmul.py (:14-45 segment, :48-93 grou
 test/csrc/ops/test_matmul.cpp.  Tolerances: fp32 <= 1e-5 relative (norm-wise, SURVEY.md 8(a) M2);
 bf16/fp16 within one rounding of the correctly rounded result.
 """
-import os.path as osp
-
 import numpy as np
 import pytest
 import torch
@@ -13,10 +11,11 @@ import torch
 import oracle
 import pyg_lib_amd
 from pyg_lib_amd import ops
+from tests.golden import parts
 
 pytestmark = pytest.mark.gpu
 
-GOLD = np.load(osp.join(osp.dirname(__file__), 'golden', 'matmul_golden.npz'))
+GOLD = parts.load('matmul_golden')
 DEV = 'cuda:0'
 
 

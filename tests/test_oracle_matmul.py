@@ -8,8 +8,9 @@ import numpy as np
 import pytest
 
 import oracle
+from tests.golden import parts
 
-GOLD = np.load(osp.join(osp.dirname(__file__), 'golden', 'matmul_golden.npz'))
+GOLD = parts.load('matmul_golden')
 WORDS = np.load(osp.join(osp.dirname(__file__), 'golden', 'mt19937_words.npz'))
 
 

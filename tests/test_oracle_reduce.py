@@ -1,5 +1,5 @@
 """Pins the scatter / segment_coo / gather_coo / index_sort oracle against outputs of the REAL
-reference CPU kernels (tests/golden/reduce_golden.npz, recorded through oracle/_ref).  CPU only."""
+reference CPU kernels (tests/golden/reduce_golden.part*.npz, recorded through oracle/_ref).  CPU only."""
 import numpy as np
 import pytest
 

@@ -1,5 +1,5 @@
 """Parity of the HIP index_sort / scatter_* / segment_*_coo / gather_coo with the real reference's
-recorded outputs (tests/golden/reduce_golden.npz) and with the oracle.
+recorded outputs (tests/golden/reduce_golden.part*.npz) and with the oracle.
 
 Modelled on the reference's test/ops/test_index_sort.py, test_scatter.py, test_segment_coo.py and
 test_composite.py.  Integer results, min/max values, arg indices, gathers and sort permutations are

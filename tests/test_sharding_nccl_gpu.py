@@ -43,7 +43,7 @@ def test_bench_self_launches_nccl_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env['HSA_ENABLE_IPC_MODE_LEGACY'] = '0'
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                          '--scale', '0.1', '--no-sampler', '--no-cpu-baseline'],
+                          '--scale', '0.1', '--full', '--no-sampler', '--no-cpu-baseline'],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])

@@ -1,12 +1,14 @@
 #!/bin/bash
 # Round-end evidence on the GPU box: bench lines, rocprofv3 kernel stats of the same command, PMC passes (own runs).
 #   tools/profile_round.sh <out dir under gpurun_out/>
+REPO="$(cd "$(dirname "$0")/.." && pwd)"
 R=/root/repo/gpurun_out/$1
 mkdir -p $R
 cd /tmp && export TMPDIR=/tmp
-python /root/repo/bench.py > $R/bench_full_1.json 2> $R/bench_full_1.err
-python /root/repo/bench.py > $R/bench_full_2.json 2> $R/bench_full_2.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_bench -o bench -- python /root/repo/bench.py --steps 10 --warmup 3 > $R/bench_under_rocprof.log 2>&1
+# the secondary figures (roofline, legs, sampler, CPU baselines) are in the bench line with --full only
+python "$REPO/bench.py" --full > $R/bench_full_1.json 2> $R/bench_full_1.err
+python "$REPO/bench.py" --full > $R/bench_full_2.json 2> $R/bench_full_2.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_bench -o bench -- python "$REPO/bench.py" --full --steps 10 --warmup 3 > $R/bench_under_rocprof.log 2>&1
 # C2 only (no legs): the headline kernel's average must be reproducible from profiles/ alone -- the full bench's stats mix
 # the segment_short leg into the same kernel name; same box, same options as the PMC passes below
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_c2 -o c2 -- python /root/repo/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-sampler --no-legs > $R/c2_under_rocprof.log 2>&1
@@ -33,4 +35,4 @@ done
 PYTHONPATH=/root/repo python /root/repo/tools/rgcn_item_balance.py 768 > $R/c5_item_balance.txt 2>&1
 rocm-smi --showmemorypartition --showcomputepartition --showclocks --showpower --showperflevel > $R/rocm_smi.txt 2>&1
 cp /root/repo/gpurun_out/gpu_health.txt $R/gpu_health.txt 2>/dev/null
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 /root/repo/bench.py --gpus 2 --debug-one-device --no-cpu-baseline > $R/bench_2rank_debug.json 2> $R/bench_2rank_debug.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 "$REPO/bench.py" --gpus 2 --debug-one-device --full --no-cpu-baseline > $R/bench_2rank_debug.json 2> $R/bench_2rank_debug.err
