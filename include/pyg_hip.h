@@ -57,6 +57,7 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *   9: pyg_hip_random_walk, pyg_hip_subgraph (added after the original hot-path contract).
  *   8: round 6 -- pyg_hip_segment_csr_ws / pyg_hip_gather_csr_ws / pyg_hip_csr_hub_workspace_size (scratch for hub rows);
  *      pyg_hip_scatter uses the dead parts of its workspace for the same purpose (no change for its callers).
  *   7: round 6 -- pyg_hip_rgcn_relation::scatter_rows (rows of the relation's destination segment).
@@ -66,7 +67,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 8
+#define PYG_HIP_ABI_VERSION 9
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -574,6 +575,43 @@ PYG_HIP_API int pyg_hip_relabel_neighborhood(const int64_t* seed, int64_t num_se
 PYG_HIP_API int pyg_hip_segment_concat(const int64_t* const* bases, const int64_t* part, const int64_t* begin,
                                        const int64_t* dst_off, int64_t n, const int64_t* fill, int64_t* out,
                                        int64_t total, void* stream);
+
+/* ---- random_walk / subgraph ---------------------------------------------------------------- */
+
+/*
+ * Uniform random walks.  Replaces pyg::random_walk (schema pyg_lib/csrc/sampler/random_walk.cpp:29-32; CUDA kernel
+ * sampler/cuda/random_walk_kernel.cu:27-88).  index_dtype is PYG_I32 or PYG_I64 and types rowptr (num_nodes + 1),
+ * col (num_edges), seed (num_seeds) and out ([num_seeds, walk_length + 1], row-major, seeds in column 0).
+ * `rand` holds walk_length x num_seeds float32 uniforms in [0, 1) (the caller draws them as the reference does:
+ * at::rand({walk_length, num_seeds}) on the seeds' device); step j of walk i uses rand[j * num_seeds + i]:
+ * v <- col[rowptr[v] + min(trunc(float(u) * float(deg)), deg - 1)] when deg = rowptr[v + 1] - rowptr[v] > 0, else v
+ * stays (the reference's "fake self-loop").  A node outside [0, num_nodes) -- a seed or a col entry -- and a row whose
+ * rowptr pair leaves [0, num_edges] are treated as isolated: nothing outside rowptr / col is read (the reference's
+ * behaviour there is undefined).  walk_length < 0 fails with PYG_HIP_ERR_INVALID.  Does not synchronise.
+ * A block's output tile is written through LDS (16-byte stores) where it fits in 64 KiB; PYG_HIP_WALK_STAGE=0 writes
+ * every step straight from registers instead (A/B switch).
+ */
+PYG_HIP_API int pyg_hip_random_walk(int index_dtype, const void* rowptr, int64_t num_nodes, const void* col,
+                                    int64_t num_edges, const void* seed, int64_t num_seeds, const float* rand,
+                                    int64_t walk_length, void* out, void* stream);
+
+/*
+ * Induced subgraph of a node list.  Replaces pyg::subgraph (schema pyg_lib/csrc/sampler/subgraph.cpp:30-32; CPU kernel
+ * sampler/cpu/subgraph_kernel.cpp:13-92 with the Mapper of sampler/cpu/mapper.h; the reference has no device kernel).
+ * index_dtype is PYG_I32 or PYG_I64 and types rowptr (num_nodes + 1), col (num_edges), nodes (num_selected) and every
+ * output.  out_rowptr (caller-allocated, num_selected + 1 entries) has one row per POSITION of `nodes`; the row holds
+ * the kept neighbours of nodes[i] in CSR order.  The local id of a node is the rank of its first occurrence among the
+ * distinct nodes of `nodes` (Mapper::insert order), so a duplicated node repeats its row and its id is that of the first
+ * occurrence.  *out_col / *out_edge_id (positions in col of the kept edges; NULL unless return_edge_id) come from
+ * host->alloc (only alloc / free of `host` are used) and hold *num_out_edges entries.  A node id outside
+ * [0, num_nodes), in `nodes` or in col, is never a member (an entry of `nodes` gets an empty row and no local id).
+ * Deterministic.  Synchronises `stream` once, to size the edge outputs (the reference reads out_rowptr[-1] the same
+ * way); num_selected = 0 does not synchronise.
+ */
+PYG_HIP_API int pyg_hip_subgraph(int index_dtype, const void* rowptr, int64_t num_nodes, const void* col,
+                                 int64_t num_edges, const void* nodes, int64_t num_selected, int return_edge_id,
+                                 const pyg_hip_sampler_host* host, void* out_rowptr, void** out_col, void** out_edge_id,
+                                 int64_t* num_out_edges, void* stream);
 
 /* ---- index_sort ---------------------------------------------------------------------------- */
 

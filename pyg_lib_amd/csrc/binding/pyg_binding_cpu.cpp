@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "binding_common.h"
+#include "word_engine.h"
 
 namespace pyg_amd {
 namespace cpu {
@@ -35,44 +36,6 @@ typedef std::string rel_type;
 typedef std::tuple<std::string, std::string, std::string> edge_type;
 
 inline rel_type rel_name(const edge_type& k) { return std::get<0>(k) + "__" + std::get<1>(k) + "__" + std::get<2>(k); }
-
-// ---------------------------------------------------------------------------------------------------------------
-// random integers: 128 prefetched 64-bit words, consumed 16 / 32 / 64 bits at a time from the last word down
-// ---------------------------------------------------------------------------------------------------------------
-class WordEngine {
- public:
-  WordEngine() {
-    buf_ = at::randint(std::numeric_limits<int64_t>::min(), std::numeric_limits<int64_t>::max(), {kWords}, at::kLong);
-    words_ = buf_.data_ptr<int64_t>();
-  }
-  // uniform in [0, range)
-  uint64_t below(uint64_t range) {
-    const int need = range < (1ull << 16) ? 16 : (range < (1ull << 32) ? 32 : 64);
-    if (bits_ < need) {
-      if (pos_ > 0) {
-        --pos_;
-      } else {
-        buf_.random_(std::numeric_limits<int64_t>::min(), std::numeric_limits<int64_t>::max());
-        pos_ = kWords - 1;
-      }
-      bits_ = 64;  // whatever was left of the previous word is dropped
-    }
-    uint64_t w = static_cast<uint64_t>(words_[pos_]);
-    const uint64_t mask = need == 64 ? ~0ull : ((1ull << need) - 1);
-    const uint64_t r = (w & mask) % range;
-    w = need == 64 ? 0 : (w >> need);
-    words_[pos_] = static_cast<int64_t>(w);
-    bits_ -= need;
-    return r;
-  }
-
- private:
-  static constexpr int kWords = 128;
-  Tensor buf_;
-  int64_t* words_;
-  int pos_ = kWords - 1;
-  int bits_ = 64;
-};
 
 // ---------------------------------------------------------------------------------------------------------------
 // global -> local ids in order of first appearance

@@ -1,4 +1,5 @@
-"""``pyg_lib.sampler`` surface of the hot path: ``neighbor_sample`` and ``hetero_neighbor_sample``.
+"""``pyg_lib.sampler`` surface of the hot path: ``neighbor_sample``, ``hetero_neighbor_sample``, ``subgraph`` and
+``random_walk``.
 
 Argument names, order, defaults and the shape of the results follow the reference's Python front
 (pyg_lib/sampler/__init__.py:11-200) so that callers (PyG's ``NeighborSampler``) need no change; everything
@@ -6,7 +7,9 @@ behind them is this repository's: the operators ``torch.ops.pyg.neighbor_sample`
 ``hetero_neighbor_sample`` are registered by ``libpyg.so`` and run the whole multi-hop expansion -- sampling,
 first-occurrence relabelling, per-hop bookkeeping -- on the HIP device that holds the graph.  The random
 stream is the global CPU generator's (continued on the device), so ``torch.manual_seed(s)`` reproduces the
-reference's samples bit for bit.  CPU tensors take the ``CPU`` dispatch key's restatement of the same drivers
+reference's samples bit for bit.  ``random_walk`` and ``subgraph`` (csrc/hip/walk.hip) follow the same pattern: the
+walk draws the reference CUDA kernel's uniforms with torch and agrees with it bit for bit; the induced subgraph is
+deterministic on either device.  CPU tensors take the ``CPU`` dispatch key's restatement of the same drivers
 (csrc/binding/pyg_binding_cpu.cpp: host logic for tests and tooling, not a performance path).
 """
 from typing import Dict, List, Optional, Tuple
@@ -184,6 +187,60 @@ def hetero_neighbor_sample_batched(rowptr_dict: Dict[EdgeType, Tensor], col_dict
              nph[b], to_edge_keys(eph[b])) for b in range(len(seed_dicts))]
 
 
+def subgraph(
+    rowptr: Tensor,
+    col: Tensor,
+    nodes: Tensor,
+    return_edge_id: bool = True,
+) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    r"""Returns the induced subgraph of the graph given by
+    :obj:`(rowptr, col)`, containing only the nodes in :obj:`nodes`.
+
+    Args:
+        rowptr: Compressed source node indices.
+        col: Target node indices.
+        nodes: Node indices of the induced subgraph.
+        return_edge_id: If set to :obj:`False`, will not
+            return the indices of edges of the original graph contained in the
+            induced subgraph.
+
+    Returns:
+        Compressed source node indices and target node indices of the induced
+        subgraph.
+        In addition, may return the indices of edges of the original graph.
+    """
+    return torch.ops.pyg.subgraph(rowptr, col, nodes, return_edge_id)
+
+
+def random_walk(
+    rowptr: Tensor,
+    col: Tensor,
+    seed: Tensor,
+    walk_length: int,
+    p: float = 1.0,
+    q: float = 1.0,
+) -> Tensor:
+    r"""Samples random walks of length :obj:`walk_length` from all node
+    indices in :obj:`seed` in the graph given by :obj:`(rowptr, col)`, as
+    described in the `"node2vec: Scalable Feature Learning for Networks"
+    <https://arxiv.org/abs/1607.00653>`_ paper.
+
+    Args:
+        rowptr: Compressed source node indices.
+        col: Target node indices.
+        seed: Seed node indices from where random walks start.
+        walk_length: The walk length of a random walk.
+        p: Likelihood of immediately revisiting a node in the walk.
+        q: Control parameter to interpolate between breadth-first strategy and
+            depth-first strategy.
+
+    Returns:
+        A tensor of shape :obj:`[seed.size(0), walk_length + 1]`, holding the
+        nodes indices of each walk for each seed node.
+    """
+    return torch.ops.pyg.random_walk(rowptr, col, seed, walk_length, p, q)
+
+
 def release_table_cache() -> int:
     """Hands the node tables the sampler keeps between calls (up to 8 x 128 MiB per device) back to the caching allocator;
     returns how many are still in use by running calls.  ``torch.cuda.empty_cache()`` afterwards returns the memory to
@@ -212,5 +269,5 @@ def last_mode() -> str:
     return L.pyg_hip_sampler_last_mode().decode()
 
 
-__all__ = ['neighbor_sample', 'hetero_neighbor_sample', 'neighbor_sample_batched', 'hetero_neighbor_sample_batched',
-           'release_table_cache', 'last_mode', 'rng_carry_stats']
+__all__ = ['neighbor_sample', 'hetero_neighbor_sample', 'subgraph', 'random_walk', 'neighbor_sample_batched',
+           'hetero_neighbor_sample_batched', 'release_table_cache', 'last_mode', 'rng_carry_stats']
