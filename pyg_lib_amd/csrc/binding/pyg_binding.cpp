@@ -276,10 +276,11 @@ static std::vector<Tensor> grouped_matmul_impl(const at::TensorList input, const
                                       ws.data_ptr(), (size_t)ws.numel(), matmul_flags(input[0].scalar_type()),
                                       current_stream(input[0])));
   // the outputs: one dispatcher call each, made while the kernel runs (aliases of the pool that are NOT tracked as
-  // views, see above)
+  // views, see above).  as_strided takes an offset into the STORAGE: a caller's pool may be a view that starts inside it.
   at::AutoDispatchBelowADInplaceOrView untracked;
+  const int64_t base = pool.storage_offset();
   for (size_t i = 0; i < G; ++i)
-    outs.push_back(pool.as_strided({input[i].size(0), other[i].size(-1)}, {other[i].size(-1), 1}, offs[i]));
+    outs.push_back(pool.as_strided({input[i].size(0), other[i].size(-1)}, {other[i].size(-1), 1}, base + offs[i]));
   return outs;
 }
 
