@@ -9,6 +9,9 @@
 #include <ATen/record_function.h>
 #include <dlfcn.h>
 
+#include <string>
+#include <tuple>
+
 #include "pyg_hip.h"
 
 namespace pyg_amd {
@@ -82,6 +85,57 @@ inline hipStream_t current_hip_stream(c10::DeviceIndex index) {
 
 inline void* current_stream(const Tensor& t) {
   return static_cast<void*>(current_hip_stream((c10::DeviceIndex)t.get_device()));
+}
+
+// ---- the stream-bound allocator host of a pyg_hip_sampler_host (include/pyg_hip.h) -------------------------------------
+// `user` of the alloc / free callbacks: blocks come from the caching allocator on `stream`; an allocator exception is kept
+// in `error` (the C-ABI cannot carry it) and the library sees a null block.
+struct AllocHost {
+  hipStream_t stream = nullptr;
+  std::string error;
+};
+
+inline void* host_alloc(void* user, size_t bytes) {
+  auto* h = static_cast<AllocHost*>(user);
+  try {
+    return alloc::raw_alloc_with_stream(bytes ? bytes : 16, h->stream);
+  } catch (const std::exception& e) {
+    h->error = e.what();
+    return nullptr;
+  }
+}
+
+inline void host_free(void*, void* ptr) {
+  if (ptr) alloc::raw_delete(ptr);
+}
+
+// a block the library got from host_alloc and returned as a result: the tensor owns it from here on
+inline Tensor adopt(void* ptr, at::IntArrayRef sizes, const at::TensorOptions& opts) {
+  return at::from_blob(
+      ptr, sizes, [](void* p) { alloc::raw_delete(p); }, opts);
+}
+
+// ---- heterogeneous graphs and the samplers' modes (device and CPU key) -------------------------------------------------
+// pyg_lib/csrc/utils/types.h:10-12
+typedef std::string node_type;
+typedef std::string rel_type;
+typedef std::tuple<std::string, std::string, std::string> edge_type;
+
+inline rel_type rel_key(const edge_type& key) {
+  return std::get<0>(key) + "__" + std::get<1>(key) + "__" + std::get<2>(key);
+}
+
+// precondition checks of the reference kernel, sampler/cpu/neighbor_kernel.cpp:34-36,354-380,501
+inline void check_modes(bool has_node_time, bool has_edge_time, bool has_seed_time, bool has_weight, bool directed,
+                        bool disjoint, const std::string& temporal_strategy) {
+  TORCH_CHECK(temporal_strategy == "uniform" || temporal_strategy == "last", "No valid temporal strategy found");
+  TORCH_CHECK(!has_node_time || disjoint, "Temporal sampling needs to create disjoint subgraphs");
+  TORCH_CHECK(!has_edge_time || disjoint, "Temporal sampling needs to create disjoint subgraphs");
+  TORCH_CHECK(!(has_node_time && has_edge_time), "Only one of node-level or edge-level sampling is supported ");
+  TORCH_CHECK(!has_edge_time || has_seed_time, "Seed time needs to be specified");
+  TORCH_CHECK(!(has_node_time && has_weight), "Biased node temporal sampling not yet supported");
+  TORCH_CHECK(!(has_edge_time && has_weight), "Biased edge temporal sampling not yet supported");
+  TORCH_CHECK(directed, "Undirected subgraphs not yet supported");
 }
 
 // `flags` of pyg_hip_segment_matmul / pyg_hip_grouped_matmul (include/pyg_hip.h) for a call made on this thread:

@@ -31,12 +31,6 @@
 namespace pyg_amd {
 namespace cpu {
 
-typedef std::string node_type;
-typedef std::string rel_type;
-typedef std::tuple<std::string, std::string, std::string> edge_type;
-
-inline rel_type rel_name(const edge_type& k) { return std::get<0>(k) + "__" + std::get<1>(k) + "__" + std::get<2>(k); }
-
 // ---------------------------------------------------------------------------------------------------------------
 // global -> local ids in order of first appearance
 // ---------------------------------------------------------------------------------------------------------------
@@ -306,19 +300,6 @@ struct Held {
   }
 };
 
-static void check_modes(bool has_node_time, bool has_edge_time, bool has_seed_time, bool has_weight, bool directed,
-                        bool disjoint, const std::string& temporal_strategy) {
-  // sampler/cpu/neighbor_kernel.cpp:34-36,354-380,501
-  TORCH_CHECK(temporal_strategy == "uniform" || temporal_strategy == "last", "No valid temporal strategy found");
-  TORCH_CHECK(!has_node_time || disjoint, "Temporal sampling needs to create disjoint subgraphs");
-  TORCH_CHECK(!has_edge_time || disjoint, "Temporal sampling needs to create disjoint subgraphs");
-  TORCH_CHECK(!(has_node_time && has_edge_time), "Only one of node-level or edge-level sampling is supported ");
-  TORCH_CHECK(!has_edge_time || has_seed_time, "Seed time needs to be specified");
-  TORCH_CHECK(!(has_node_time && has_weight), "Biased node temporal sampling not yet supported");
-  TORCH_CHECK(!(has_edge_time && has_weight), "Biased edge temporal sampling not yet supported");
-  TORCH_CHECK(directed, "Undirected subgraphs not yet supported");
-}
-
 std::tuple<Tensor, Tensor, Tensor, c10::optional<Tensor>, std::vector<int64_t>, std::vector<int64_t>>
 neighbor_sample_cpu(const Tensor& rowptr, const Tensor& col, const Tensor& seed, const std::vector<int64_t>& num_neighbors,
                     const c10::optional<Tensor>& node_time, const c10::optional<Tensor>& edge_time,
@@ -385,7 +366,7 @@ hetero_neighbor_sample_cpu(const std::vector<node_type>& node_types, const std::
   size_t hops = 0;
   for (size_t e = 0; e < edge_types.size(); ++e) {
     const auto& k = edge_types[e];
-    const auto name = rel_name(k);
+    const auto name = rel_key(k);
     TORCH_CHECK(type_index.count(std::get<0>(k)) && type_index.count(std::get<2>(k)),
                 "hetero_neighbor_sample: edge type names an unknown node type");
     const Tensor& rowptr = rowptr_dict.at(name);
@@ -442,7 +423,7 @@ hetero_neighbor_sample_cpu(const std::vector<node_type>& node_types, const std::
     out_nph.insert(node_types[t], sampler.nodes(static_cast<int>(t)).per_hop);
   }
   for (size_t e = 0; e < edge_types.size(); ++e) {
-    const auto name = rel_name(edge_types[e]);
+    const auto name = rel_key(edge_types[e]);
     const EdgeList& el = sampler.edges(e);
     const Tensor rows = h.out(el.rows), cols = h.out(el.cols);
     out_row.insert(name, csc ? cols : rows);
@@ -521,7 +502,7 @@ std::tuple<Tensor, Tensor> index_sort_cpu(const Tensor& input, const at::optiona
 
 }  // namespace cpu
 
-// used by the BackendSelect kernel of hetero_neighbor_sample (pyg_binding.cpp): Dict values cannot drive dispatch
+// used by the BackendSelect kernel of hetero_neighbor_sample (pyg_binding_sampler.cpp): Dict values cannot drive dispatch
 std::tuple<c10::Dict<std::string, Tensor>, c10::Dict<std::string, Tensor>, c10::Dict<std::string, Tensor>,
            c10::optional<c10::Dict<std::string, Tensor>>, c10::Dict<std::string, std::vector<int64_t>>,
            c10::Dict<std::string, std::vector<int64_t>>>

@@ -121,12 +121,6 @@ std::tuple<Tensor, Tensor, std::optional<Tensor>, std::vector<int64_t>> merge_sa
 
 }  // namespace
 
-// sampler/dist_relabel.cpp:71-76, sampler/dist_merge_outputs.cpp:51-55
-typedef std::string node_type;
-typedef std::string rel_type;
-typedef std::tuple<std::string, std::string, std::string> edge_type;
-inline rel_type rel_of(const edge_type& k) { return std::get<0>(k) + "__" + std::get<1>(k) + "__" + std::get<2>(k); }
-
 // pyg::hetero_relabel_neighborhood (sampler/cpu/dist_relabel_kernel.cpp:96-262).  Every node type has one
 // Mapper and its sampled list is consumed strictly in order, so the local ids are computed per node type
 // (pyg_hip_relabel_nodes) and every (edge type, layer) is a segment: rows = the layer's source range expanded
@@ -191,7 +185,7 @@ std::tuple<c10::Dict<rel_type, Tensor>, c10::Dict<rel_type, Tensor>> hetero_rela
   TORCH_CHECK(device.has_value(), "hetero_relabel_neighborhood: no node types");
   DeviceGuard guard(device.value());
   const auto opts = at::TensorOptions().dtype(at::kLong).device(device.value());
-  const size_t num_layers = num_sampled_neighbors_per_node_dict.at(rel_of(edge_types[0])).size();
+  const size_t num_layers = num_sampled_neighbors_per_node_dict.at(rel_key(edge_types[0])).size();
   // host walk of the (layer, edge type) segments (:194-256)
   std::unordered_map<std::string, int64_t> dst_pos, src_off;
   for (const auto& t : node_types) {
@@ -205,10 +199,10 @@ std::tuple<c10::Dict<rel_type, Tensor>, c10::Dict<rel_type, Tensor>> hetero_rela
   std::vector<std::vector<Seg>> segs(edge_types.size());
   std::vector<std::pair<int64_t, int64_t>> slice(edge_types.size());
   for (size_t e = 0; e < edge_types.size(); ++e)
-    slice[e] = {0, (int64_t)num_sampled_neighbors_per_node_dict.at(rel_of(edge_types[e]))[0].size()};
+    slice[e] = {0, (int64_t)num_sampled_neighbors_per_node_dict.at(rel_key(edge_types[e]))[0].size()};
   // the Dict hands out copies: keep them alive while Seg points into them
   std::vector<std::vector<std::vector<int64_t>>> counts_keep(edge_types.size());
-  for (size_t e = 0; e < edge_types.size(); ++e) counts_keep[e] = num_sampled_neighbors_per_node_dict.at(rel_of(edge_types[e]));
+  for (size_t e = 0; e < edge_types.size(); ++e) counts_keep[e] = num_sampled_neighbors_per_node_dict.at(rel_key(edge_types[e]));
   for (size_t ell = 0; ell < num_layers; ++ell) {
     for (size_t e = 0; e < edge_types.size(); ++e) {
       const auto& k = edge_types[e];
@@ -265,11 +259,11 @@ std::tuple<c10::Dict<rel_type, Tensor>, c10::Dict<rel_type, Tensor>> hetero_rela
       row = meta.narrow(0, nsrc + 1, nsrc).index_select(0, row);  // list position -> source id
     }
     if (!csc) {
-      out_row.insert(rel_of(k), row);
-      out_col.insert(rel_of(k), col);
+      out_row.insert(rel_key(k), row);
+      out_col.insert(rel_key(k), col);
     } else {
-      out_row.insert(rel_of(k), col);
-      out_col.insert(rel_of(k), row);
+      out_row.insert(rel_key(k), col);
+      out_col.insert(rel_key(k), row);
     }
   }
   return std::make_tuple(out_row, out_col);

@@ -61,30 +61,6 @@ Tensor random_walk_cuda(const Tensor& rowptr, const Tensor& col, const Tensor& s
   return out;
 }
 
-struct AllocHost {
-  hipStream_t stream;
-  std::string error;
-};
-
-void* walk_alloc(void* user, size_t bytes) {
-  auto* h = static_cast<AllocHost*>(user);
-  try {
-    return alloc::raw_alloc_with_stream(bytes ? bytes : 16, h->stream);
-  } catch (const std::exception& e) {
-    h->error = e.what();
-    return nullptr;
-  }
-}
-
-void walk_free(void*, void* ptr) {
-  if (ptr) alloc::raw_delete(ptr);
-}
-
-Tensor adopt(void* ptr, int64_t n, const at::TensorOptions& opts) {
-  return at::from_blob(
-      ptr, {n}, [](void* p) { alloc::raw_delete(p); }, opts);
-}
-
 std::tuple<Tensor, Tensor, c10::optional<Tensor>> subgraph_cuda(const Tensor& rowptr, const Tensor& col,
                                                                 const Tensor& nodes, bool return_edge_id) {
   PYG_TRACE("pyg::subgraph");
@@ -100,7 +76,7 @@ std::tuple<Tensor, Tensor, c10::optional<Tensor>> subgraph_cuda(const Tensor& ro
   const int64_t M = nodes.size(0);
   auto out_rowptr = at::empty({M + 1}, rowptr.options());
   AllocHost ah{current_hip_stream((c10::DeviceIndex)nodes.get_device()), {}};
-  pyg_hip_sampler_host host{&ah, &walk_alloc, &walk_free, nullptr, nullptr};
+  pyg_hip_sampler_host host{&ah, &host_alloc, &host_free, nullptr, nullptr};
   void* out_col = nullptr;
   void* out_eid = nullptr;
   int64_t K = 0;
@@ -108,9 +84,9 @@ std::tuple<Tensor, Tensor, c10::optional<Tensor>> subgraph_cuda(const Tensor& ro
                                   col_c.numel(), nodes_c.data_ptr(), M, return_edge_id ? 1 : 0, &host, out_rowptr.data_ptr(),
                                   &out_col, &out_eid, &K, static_cast<void*>(ah.stream));
   TORCH_CHECK(rc == PYG_HIP_OK, pyg_hip_last_error(), ah.error.empty() ? "" : " (", ah.error, ah.error.empty() ? "" : ")");
-  Tensor col_out = adopt(out_col, K, col.options());
+  Tensor col_out = adopt(out_col, {K}, col.options());
   c10::optional<Tensor> eid_out = c10::nullopt;
-  if (return_edge_id) eid_out = adopt(out_eid, K, col.options());
+  if (return_edge_id) eid_out = adopt(out_eid, {K}, col.options());
   return std::make_tuple(out_rowptr, col_out, eid_out);
 }
 
