@@ -86,6 +86,8 @@ PYG_HIP_API const char* pyg_hip_arch(void);
  * word: per call (PYG_HIP_SCATTER_CAS, PYG_HIP_RGCN_CAS) or as the process-wide default below (0 = hardware adds,
  * 1 = CAS loops; initial value from the environment, PYG_HIP_FLOAT_ATOMICS=hw|cas).  Same sums up to the order the adds
  * land in; the CAS form is 1.5 - 3x slower on contended rows.  Returns the previous default.
+ * Denormals: both flavours keep them -- measured on gfx950, the hardware adds (f32, f64 and the packed 16-bit pairs) return
+ * exact denormal sums bit for bit like the CAS loops, the atomic-free paths and the CPU (tests/test_special_values_gpu.py).
  */
 PYG_HIP_API int pyg_hip_set_float_atomic_mode(int mode);
 /* What the calling process's LAST launch of an atomically accumulating kernel was (thread-local text buffer): operator,
@@ -678,6 +680,10 @@ typedef enum {
  *             reference's sequential CPU loop (ops/cpu/scatter_kernel.cpp:29-127).  Layouts without an atomic-free
  *             kernel (element-wise indices, B > 1 unsorted) and floating MUL return PYG_HIP_ERR_UNSUPPORTED with the
  *             bit set.  The torch binding sets it when torch.are_deterministic_algorithms_enabled().
+ * Non-finite values and signed zeros follow the reference's sequential loops on every path: a NaN never
+ * wins a min / max (a bucket of NaN only counts as empty) and makes a sum NaN; +0 and -0 tie, the first one seen stays
+ * (value bits and arg, also on the atomic path); a sum of nothing but -0 into a caller's -0 stays -0, into a fresh output
+ * it is +0; denormal sums are kept.
  */
 #define PYG_HIP_SCATTER_SORTED 1
 #define PYG_HIP_SCATTER_FRESH_SUM 2
@@ -723,6 +729,9 @@ PYG_HIP_API int pyg_hip_gather_coo(int dtype, const void* src, const int64_t* in
  * kernel for every dtype unless rows are long and few (then lanes split a row) or longer than 512
  * positions per lane (4096 for rows narrower than 64 bytes: hub rows, see pyg_hip_segment_csr_ws); floating
  * sums of such rows differ by rounding, min/max/arg stay exact, and every run gives the same bits.
+ * Non-finite values and signed zeros, the same on every row kernel, lane-split, hub or not: strict
+ * compares -- a NaN in `src` never wins, a NaN / -0 / identity in a caller's `out` slot stays with arg = E unless strictly
+ * beaten, +0 and -0 tie and the first position wins; {+Inf, -Inf} or a NaN make a sum / mean NaN; -0 + {-0, ...} stays -0.
  */
 PYG_HIP_API int pyg_hip_segment_csr(int op, int dtype, const void* src, const int64_t* indptr,
                                     int64_t indptr_slice_stride, void* out, int64_t* arg_out, int fresh,
@@ -763,6 +772,8 @@ PYG_HIP_API int pyg_hip_gather_csr_ws(int dtype, const void* src, const int64_t*
  * (group, outer, inner) head; `out` must be zero-filled by the caller (positions outside every group
  * stay 0).  float32 / float64.  Replaces pyg::softmax_csr / pyg::softmax_csr_backward (schemas
  * ops/softmax.cpp:46-53; CPU only in the reference: ops/cpu/softmax_kernel.cpp:58-222).
+ * The maximum starts from lowest(), not -Inf: a -Inf logit gives exactly 0 and the softmax of the rest;
+ * a group of -Inf only, or with a +Inf or a NaN, is NaN in that group and head only; a one-element group is exactly 1.
  */
 PYG_HIP_API int pyg_hip_softmax_csr(int dtype, const void* src, const int64_t* ptr, void* out, int64_t outer,
                                     int64_t D, int64_t inner, int64_t groups, void* stream);

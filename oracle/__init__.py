@@ -350,6 +350,10 @@ def _declare_reduce(L):
     L.oracle_softmax_csr_backward.restype = None
     L.oracle_softmax_csr_backward.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
                                               c.c_int64, c.c_int64]
+    L.oracle_softmax_csr_f64.restype = None
+    L.oracle_softmax_csr_f64.argtypes = L.oracle_softmax_csr.argtypes
+    L.oracle_softmax_csr_backward_f64.restype = None
+    L.oracle_softmax_csr_backward_f64.argtypes = L.oracle_softmax_csr_backward.argtypes
     L._reduce_declared = True
 
 
@@ -454,6 +458,35 @@ def segment_sum_coo(src, index, out=None, dim_size=None, dtype=None):
         if rc != 0:
             raise RuntimeError('oracle_segment_sum_coo: index out of range')
     return out
+
+
+def _div_count(s, cnt, dtype):
+    """s / cnt in the storage type's arithmetic (16-bit types divide in float32 and round once)."""
+    if dtype == BF16:
+        return f32_to_bf16_bits(bf16_bits_to_f32(s) / cnt.astype(np.float32))
+    if s.dtype == np.float16:
+        return (s.astype(np.float32) / cnt.astype(np.float32)).astype(np.float16)
+    return (s / cnt.astype(s.dtype)).astype(s.dtype)
+
+
+def segment_mean_coo(src, index, out=None, dim_size=None, dtype=None):
+    """segment_coo_kernel.cpp:187-331: every run's sum starts from 0 and OVERWRITES its bucket; then the whole output --
+    untouched buckets of a caller's `out` included -- is divided by max(count, 1)."""
+    src = np.ascontiguousarray(src)
+    idx, dim, B, E, K = _coo_shapes(src, index)
+    if out is None and dim_size is None:
+        dim_size = 0 if idx.size == 0 else int(idx[..., -1].max()) + 1
+    n = dim_size if out is None else np.asarray(out).shape[dim]
+    s = segment_sum_coo(src, index, None, n, dtype)
+    if src.size == 0:
+        return s if out is None else np.ascontiguousarray(out).copy()
+    cnt = np.zeros(idx.shape[:dim] + (n,), dtype=np.float64)
+    for b in np.ndindex(*idx.shape[:dim]):
+        np.add.at(cnt[b], idx[b], 1)
+    touched = (cnt > 0).reshape(cnt.shape + (1,) * (src.ndim - idx.ndim))
+    res = s if out is None else np.where(np.broadcast_to(touched, s.shape), s, np.ascontiguousarray(out))
+    cnt = np.maximum(cnt, 1).reshape(touched.shape)
+    return _div_count(res, np.broadcast_to(cnt, res.shape), dtype)
 
 
 def segment_minmax_coo(op, src, index, out=None, dim_size=None, dtype=None):
@@ -606,25 +639,30 @@ def _softmax_layout(src, dim):
 
 
 def softmax_csr(src, ptr, dim=0):
+    """float32, or float64 for a float64 `src` (every other dtype is converted to float32)."""
     L = lib()
     _declare_reduce(L)
-    src = np.ascontiguousarray(src, dtype=np.float32)
+    f64 = np.asarray(src).dtype == np.float64
+    src = np.ascontiguousarray(src, dtype=np.float64 if f64 else np.float32)
     ptr = np.ascontiguousarray(ptr, dtype=np.int64)
     outer, D, inner = _softmax_layout(src, dim)
     out = np.empty_like(src)
-    L.oracle_softmax_csr(_ptr(src), _ptr(ptr), _ptr(out), outer, D, inner, ptr.size - 1)
+    (L.oracle_softmax_csr_f64 if f64 else L.oracle_softmax_csr)(_ptr(src), _ptr(ptr), _ptr(out), outer, D, inner, ptr.size - 1)
     return out
 
 
 def softmax_csr_backward(out, out_grad, ptr, dim=0):
+    """float32, or float64 for a float64 `out` (like softmax_csr: other dtypes are converted to float32)."""
     L = lib()
     _declare_reduce(L)
-    out = np.ascontiguousarray(out, dtype=np.float32)
-    out_grad = np.ascontiguousarray(out_grad, dtype=np.float32)
+    f64 = np.asarray(out).dtype == np.float64
+    out = np.ascontiguousarray(out, dtype=np.float64 if f64 else np.float32)
+    out_grad = np.ascontiguousarray(out_grad, dtype=out.dtype)
     ptr = np.ascontiguousarray(ptr, dtype=np.int64)
     outer, D, inner = _softmax_layout(out, dim)
     gin = np.empty_like(out)
-    L.oracle_softmax_csr_backward(_ptr(out), _ptr(out_grad), _ptr(ptr), _ptr(gin), outer, D, inner, ptr.size - 1)
+    (L.oracle_softmax_csr_backward_f64 if f64 else L.oracle_softmax_csr_backward)(
+        _ptr(out), _ptr(out_grad), _ptr(ptr), _ptr(gin), outer, D, inner, ptr.size - 1)
     return gin
 
 

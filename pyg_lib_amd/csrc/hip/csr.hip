@@ -87,6 +87,17 @@ __device__ __forceinline__ void pin_all(X (&a)[U]) {
   }
 }
 
+// What an accumulator that has added nothing yet holds.  For floating sums that is -0, not +0: x + -0 == x for EVERY x and
+// -0 + -0 == -0, whereas +0 turns a total of -0 into +0.  The reference's sequential loop has ONE accumulator per row, seeded
+// with the caller's `out` slot (or the +0 of a fresh output); here a row may be split over lanes, LDS partials and chunks, and
+// only the one that carries the seed may start from it -- every other starts from the identity, so that a caller's -0 plus a
+// row of nothing but -0 (or no row at all) stays -0 on every path.
+template <typename A>
+__device__ __forceinline__ A sum_identity() {
+  if constexpr (std::is_floating_point<A>::value) return A(-0.0);
+  else return A(0);
+}
+
 template <typename A>
 __device__ __forceinline__ A shfl_xor_any(A v, int mask) {
   static_assert(sizeof(A) % 4 == 0 || sizeof(A) < 4, "unsupported accumulator");
@@ -182,18 +193,18 @@ __global__ __launch_bounds__(256) void segment_csr_kernel(const T* __restrict__ 
   acc_t acc[V];
   int64_t best[V];
   if constexpr (OP == CSR_SUM) {
-    // the accumulator is seeded from the caller's `out` slot; a fresh output starts at +0 without being read (it
-    // need not be cleared either: every slot is written below -- 2 x N x K bytes less traffic)
+    // lane 0's accumulator is seeded from the caller's `out` slot; a fresh output starts at +0 without being read (it
+    // need not be cleared either: every slot is written below -- 2 x N x K bytes less traffic).  The other lanes: sum_identity()
 #pragma unroll
-    for (int i = 0; i < V; ++i) acc[i] = acc_t(0);
+    for (int i = 0; i < V; ++i) acc[i] = lane == 0 ? acc_t(0) : sum_identity<acc_t>();
     if (!fresh) {
       P cur = *reinterpret_cast<const P*>(op);
 #pragma unroll
-      for (int i = 0; i < V; ++i) acc[i] = lane == 0 ? Math<T>::up(cur.v[i]) : acc_t(0);
+      for (int i = 0; i < V; ++i) acc[i] = lane == 0 ? Math<T>::up(cur.v[i]) : sum_identity<acc_t>();
     }
   } else if constexpr (OP == CSR_MEAN) {
 #pragma unroll
-    for (int i = 0; i < V; ++i) acc[i] = acc_t(0);
+    for (int i = 0; i < V; ++i) acc[i] = lane == 0 ? acc_t(0) : sum_identity<acc_t>();
   } else {
     // (a fresh output starts from the identity without being read -- and need not be pre-filled: 2 x N x K bytes less traffic)
     P cur;
@@ -308,7 +319,7 @@ __device__ __forceinline__ void hub_span(const T* __restrict__ sp, const int64_t
   acc_t acc[V];
   int64_t best[V];
 #pragma unroll
-  for (int i = 0; i < V; ++i) acc[i] = MINMAX ? start[i] : acc_t(0), best[i] = E;
+  for (int i = 0; i < V; ++i) acc[i] = MINMAX ? start[i] : sum_identity<acc_t>(), best[i] = E;
   if (on) {
     constexpr int U = 8;
     for (int64_t e0 = pa + g.lane; e0 < pb; e0 += (int64_t)U * g.EL) {
@@ -398,14 +409,18 @@ __device__ __forceinline__ void hub_store(T* __restrict__ op, int64_t* __restric
   *reinterpret_cast<Pack<T, V>*>(op) = res;
 }
 
-// what a row's accumulation starts from: the caller's `out` slot (sum into an existing output; min / max always)
+// what a row's accumulation starts from: the caller's `out` slot (sum into an existing output; min / max always), +0 for a
+// fresh sum / a mean.  `row_start` false: the partial sum of one chunk of a longer hub -- it starts from sum_identity(), the
+// row's start is added once, where the chunks are combined
 template <typename T, int OP, int V>
-__device__ __forceinline__ void hub_seed(const T* __restrict__ op, bool on, int fresh, typename Math<T>::acc_t (&seed)[V]) {
+__device__ __forceinline__ void hub_seed(const T* __restrict__ op, bool on, int fresh, typename Math<T>::acc_t (&seed)[V],
+                                         bool row_start = true) {
   using acc_t = typename Math<T>::acc_t;
   constexpr bool MINMAX = OP == CSR_MIN || OP == CSR_MAX;
 #pragma unroll
-  for (int i = 0; i < V; ++i) seed[i] = MINMAX ? minmax_identity<T, MINMAX ? OP : CSR_MIN>() : acc_t(0);
-  if (on && !fresh && (MINMAX || OP == CSR_SUM)) {
+  for (int i = 0; i < V; ++i)
+    seed[i] = MINMAX ? minmax_identity<T, MINMAX ? OP : CSR_MIN>() : (row_start ? acc_t(0) : sum_identity<acc_t>());
+  if (on && row_start && !fresh && (MINMAX || OP == CSR_SUM)) {
     const Pack<T, V> cur = *reinterpret_cast<const Pack<T, V>*>(op);
 #pragma unroll
     for (int i = 0; i < V; ++i) seed[i] = Math<T>::up(cur.v[i]);
@@ -488,7 +503,7 @@ __global__ __launch_bounds__(256) void segment_csr_hub_chunk_kernel(const T* __r
       T* op = out + n * s.K + c;
       acc_t seed[V], tot[V];
       int64_t tb[V];
-      hub_seed<T, OP, V>(op, on && (whole || MINMAX), fresh, seed);   // (the sum of a chunk starts from 0)
+      hub_seed<T, OP, V>(op, on, fresh, seed, whole || MINMAX);   // (the sum of a chunk starts from the identity)
       hub_span<T, OP, V, PERM>(src + slice * s.E * s.K + c, perm, pa, pb, s.K, on, g, seed, part, part_best, tot, tb, s.E);
       if (on && g.lane == 0) {
         if (whole) {

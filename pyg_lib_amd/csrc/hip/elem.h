@@ -71,8 +71,9 @@ inline __device__ f16_t type_max<f16_t>() { return f16_t{0x7bff}; }
 template <>
 inline __device__ f16_t type_lowest<f16_t>() { return f16_t{0xfbff}; }
 
+// equal by VALUE: +0 == -0, a NaN equals nothing
 template <typename T>
-__device__ bool bits_equal(T a, T b) {
+__device__ bool same_value(T a, T b) {
   return Math<T>::up(a) == Math<T>::up(b);
 }
 

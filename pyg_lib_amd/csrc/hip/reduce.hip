@@ -18,7 +18,8 @@
 //   * min / max: value pass with native integer atomics (CAS loop on the reference's `<` / `>` for
 //     floating types), then an arg pass atomicMin(arg, e) over the elements that equal the final
 //     value and strictly improved the initial one -- exactly the CPU kernel's first-match rule
-//     (scatter_kernel.cpp:249-369), so values AND arg indices are bit-exact.
+//     (scatter_kernel.cpp:249-369) -- and a last pass that takes the value's bits from that position
+//     (+0 and -0 tie: the first one seen stays), so values AND arg indices are bit-exact.
 //   * mul and the 8/16-bit integer types: CAS loop on the containing 32-bit word.
 #include "common.h"
 #include "elem.h"
@@ -158,8 +159,11 @@ __global__ void scatter_elem_kernel(const T* __restrict__ src, const int64_t* __
   }
 }
 
-// arg pass of min/max: first source position whose value equals the final bucket value, provided the
-// bucket strictly improved on its initial state (init == nullptr: the type's max()/lowest()).
+// arg pass of min/max: first source position whose value EQUALS the final bucket value (by value: +0 and -0 are one
+// value, a NaN equals nothing), provided the bucket strictly improved on its initial state (init == nullptr: the type's
+// max()/lowest()).  The value pass keeps whichever of +0 / -0 its CAS loop saw first, and atomics arrive in no fixed order:
+// its zero may carry the wrong sign.  The position found here does not depend on that, and minmax_finish_kernel takes the
+// value's bits from it -- what the reference's sequential strict compare keeps: the first of the equal values.
 template <typename T, bool IS_MIN>
 __global__ void scatter_arg_kernel(const T* __restrict__ src, const int64_t* __restrict__ index,
                                    const T* __restrict__ out, const T* __restrict__ init,
@@ -174,18 +178,27 @@ __global__ void scatter_arg_kernel(const T* __restrict__ src, const int64_t* __r
     const int64_t o = (b * s.N + idx) * s.K + k;
     const T fin = out[o];
     const T v = src[i];
-    if (!bits_equal(v, fin)) continue;
+    if (!same_value(v, fin)) continue;
     const T start = init ? init[o] : (IS_MIN ? type_max<T>() : type_lowest<T>());
     const bool improved = IS_MIN ? (Math<T>::up(fin) < Math<T>::up(start)) : (Math<T>::up(fin) > Math<T>::up(start));
     if (improved) atomicMin(reinterpret_cast<long long*>(arg + o), (long long)e);
   }
 }
 
-// empty buckets (arg still the sentinel E) of a freshly allocated min/max output are reset to 0
+// last pass of the atomic min/max: a bucket with a winner takes its value's BITS from the winning position (see
+// scatter_arg_kernel: the sign of a zero); empty buckets (arg still the sentinel E) of a freshly allocated output are reset
+// to 0, those of a caller's output keep their value
 template <typename T>
-__global__ void reset_empty_kernel(T* out, const int64_t* __restrict__ arg, int64_t n, int64_t sentinel) {
+__global__ void minmax_finish_kernel(const T* __restrict__ src, T* out, const int64_t* __restrict__ arg, int fresh, Shape s) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < n && arg[i] == sentinel) out[i] = Math<T>::down((typename Math<T>::acc_t)0);
+  if (i >= s.B * s.N * s.K) return;
+  const int64_t e = arg[i];
+  if (e == s.E) {
+    if (fresh) out[i] = Math<T>::down((typename Math<T>::acc_t)0);
+    return;
+  }
+  const int64_t k = i % s.K, b = i / (s.K * s.N);
+  out[i] = src[(b * s.E + e) * s.K + k];
 }
 
 template <typename T>
@@ -260,7 +273,7 @@ struct Vec<bf16_t> {
     }
   }
   __device__ static void add_plain(bf16_t* dst, const float* a) {
-    float cur[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float cur[8] = {-0.f, -0.f, -0.f, -0.f, -0.f, -0.f, -0.f, -0.f};   // (unpack ADDS: from -0 it returns dst's values, a -0 included)
     unpack(*reinterpret_cast<const u32x4*>(dst), cur);
     u32x4 o;
     for (int i = 0; i < 4; ++i) {
@@ -300,7 +313,7 @@ struct Vec<f16_t> {
     }
   }
   __device__ static void add_plain(f16_t* dst, const float* a) {
-    float cur[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    float cur[8] = {-0.f, -0.f, -0.f, -0.f, -0.f, -0.f, -0.f, -0.f};   // (unpack ADDS: from -0 it returns dst's values, a -0 included)
     unpack(*reinterpret_cast<const u32x4*>(dst), cur);
     u32x4 o;
     for (int i = 0; i < 4; ++i) {
@@ -335,9 +348,11 @@ __global__ __launch_bounds__(256) void scatter_sum_vec_kernel(const T* __restric
     const int64_t b = t / (kv * chunks);
     const int64_t e0 = ch * R;
     const int64_t e1 = min(e0 + R, s.E);
+    // (a run's accumulator starts from -0, the identity of a floating sum: x + -0 == x for every x, -0 + -0 == -0.  From +0 a
+    // run of nothing but -0 would add +0 to a caller's -0 and turn it into +0, where the reference's sequential adds keep -0)
     float acc[VN];
 #pragma unroll
-    for (int i = 0; i < VN; ++i) acc[i] = 0.f;
+    for (int i = 0; i < VN; ++i) acc[i] = -0.f;
     int64_t cur = index[b * s.isb + e0 * s.ise];
     bool first = true;
     // batches of 8 positions: their indices and 16-byte source slices are all requested before the first is consumed
@@ -364,7 +379,7 @@ __global__ __launch_bounds__(256) void scatter_sum_vec_kernel(const T* __restric
           else Vec<T>::flush(dst, acc);
           first = false;
 #pragma unroll
-          for (int i = 0; i < VN; ++i) acc[i] = 0.f;
+          for (int i = 0; i < VN; ++i) acc[i] = -0.f;
           cur = idx;
         }
         Vec<T>::unpack(val[u], acc);
@@ -655,9 +670,10 @@ int run_scatter(int op, const void* src_, const int64_t* index, void* out_, int6
       hipLaunchKernelGGL((scatter_arg_kernel<T, false>), dim3(grid), dim3(256), 0, stream, src, index, out, init,
                          arg, s);
     }
-    if (!init)
-      hipLaunchKernelGGL((reset_empty_kernel<T>), dim3((unsigned)((outn + 255) / 256)), dim3(256), 0, stream, out,
-                         arg, outn, s.E);
+    // (integers: equal values are equal bits, only the reset of a fresh output's empty buckets is left to do)
+    if (!init || std::is_floating_point<T>::value || std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value)
+      hipLaunchKernelGGL((minmax_finish_kernel<T>), dim3((unsigned)((outn + 255) / 256)), dim3(256), 0, stream, src, out,
+                         arg, init ? 0 : 1, s);
   } else {
     return fail(PYG_HIP_ERR_INVALID, "scatter: unknown reduce op %d", op);
   }

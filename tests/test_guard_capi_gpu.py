@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests._guard import assert_no_poison, big_value, guarded, guarded_copy
+from tests._paths import CSR_CASES, _csr_shape, _lens, csr_path
 
 pytestmark = pytest.mark.gpu
 ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
@@ -430,79 +431,7 @@ def test_gather_coo(lib, dtype, B, E, K):
 
 
 # ---- CSR family ------------------------------------------------------------------------------------------------------------
-def csr_path(dtype, K, leading, rows, E, gather=False):
-    """The row kernel csr.hip picks for a shape (pick_lanes / use_stream / launch_gather restated; 16-byte aligned buffers):
-    'row1' (one lane per item), 'narrow8' (8 lanes over the positions of rows of whole 16-byte slices narrower than 64
-    bytes), 'lanes8' / 'lanes64' (lane-split long rows), 'stream' (LDS-streamed).  Returns (path, hub cut)."""
-    size = torch.empty((), dtype=dtype).element_size()
-    vmax = 16 // size
-    vec = vmax > 1 and K % vmax == 0
-    V = vmax if vec else 1
-    units = leading * rows
-    avg = leading * E // units
-    rb = K * size
-    if not gather and 1 <= K <= 16 and rb < 64 and not vec and 12 <= avg < 64:
-        return 'stream', 4096
-    chip = torch.cuda.get_device_properties(0).multi_processor_count * 2048
-    items = units * (K // V)
-    if rb < 64 and avg >= 64:
-        L, name = (64, 'lanes64') if avg >= 256 else (8, 'lanes8')
-    elif rb < 64 and rb % 16 == 0 and avg >= 16:
-        L, name = 8, 'narrow8'
-    elif avg >= 1024 and items * 8 < chip:
-        L, name = 64, 'lanes64'
-    elif avg >= 64 and items < chip:
-        L, name = 8, 'lanes8'
-    else:
-        L, name = 1, 'row1'
-    if gather and L == 1 and rb < 64 and avg >= (8 if V > 1 else 32):
-        L, name = 8, 'narrow8'
-    return name, 512 * L
-
-
-def _lens(rng, rows, lo, hi, hub=0):
-    lens = rng.integers(lo, hi, rows)
-    lens[0] = lens[-1] = 0          # empty rows first and last
-    if hub:
-        lens[rows // 3] = hub
-    return lens
-
-
-CSR_CASES = [  # name, dtype, K, leading, lengths (rows, lo, hi, hub), path
-    ('row1', torch.float32, 129, 1, (40, 0, 7, 0), 'row1'),
-    ('row1_vec', torch.float32, 8, 1, (40, 0, 7, 0), 'row1'),
-    ('row1_bf16_odd', torch.bfloat16, 65, 2, (30, 0, 9, 0), 'row1'),
-    ('narrow8', torch.float32, 4, 1, (30, 14, 27, 0), 'narrow8'),
-    ('narrow8_bf16', torch.bfloat16, 8, 3, (20, 14, 27, 0), 'narrow8'),
-    ('lanes8', torch.float32, 129, 1, (6, 100, 140, 0), 'lanes8'),
-    ('lanes8_narrow', torch.float32, 1, 1, (9, 64, 200, 0), 'lanes8'),
-    ('lanes64', torch.float32, 1, 1, (6, 400, 500, 0), 'lanes64'),
-    ('lanes64_wide', torch.float32, 17, 1, (6, 1600, 1800, 0), 'lanes64'),
-    ('stream', torch.float32, 3, 1, (40, 14, 40, 0), 'stream'),
-    ('stream_f64', torch.float64, 3, 2, (25, 14, 40, 0), 'stream'),
-    ('stream_bf16_odd', torch.bfloat16, 9, 1, (30, 14, 40, 0), 'stream'),
-    ('stream_i64', torch.int64, 3, 1, (30, 14, 40, 0), 'stream'),
-    ('hub_row1', torch.float32, 129, 1, (200, 0, 7, 700), 'row1'),
-    ('hub_row1_i64', torch.int64, 9, 2, (150, 0, 7, 2500), 'row1'),
-    ('hub_stream', torch.float32, 3, 1, (300, 14, 30, 5000), 'stream'),
-    ('hub_narrow8', torch.float32, 4, 1, (200, 14, 27, 4500), 'narrow8'),
-]
-
-
-def _csr_shape(rng, spec, leading, shared):
-    rows, lo, hi, hub = spec
-    if shared:
-        lens = _lens(rng, rows, lo, hi, hub)
-        ip = np.concatenate([[0], np.cumsum(lens)])
-        return ip[None].repeat(leading, 0), int(ip[-1])
-    # one indptr per slice, `rows + 1` apart: every slice covers all E positions (the same total, other row splits)
-    lens = _lens(rng, rows, lo, hi, hub)
-    E = int(lens.sum())
-    ips = []
-    for s in range(leading):
-        l2 = np.roll(lens[1:-1], s)
-        ips.append(np.concatenate([[0, 0], np.cumsum(l2), [E]]))
-    return np.stack(ips), E
+# csr_path / CSR_CASES / _lens / _csr_shape: tests/_paths.py (shared with tests/test_special_values_gpu.py)
 
 
 @pytest.mark.parametrize('with_ws', [False, True])

@@ -56,5 +56,17 @@ for (E, N, K, dt) in ((700_000, 120_000, 128, torch.bfloat16), (20_000_000, 2_00
     ms = timeit(lambda: ops.scatter_max(src, index, 0, None, N))
     res['scatter_max_' + tag] = dict(ms=round(ms, 3), GBps=round(bytes_sc / ms / 1e6, 1))
     del src, index, sidx, out, feat
+# scatter_min / scatter_max on the atomic path (an index below 1 << 15 entries; an element-wise index of any size): value pass,
+# arg pass and the pass that takes the value's bits from the winning position (fresh, and into a caller's `out`)
+E, N, K = 32000, 4000, 64
+src = torch.randn(E, K, device=dev, generator=g)
+index = torch.randint(0, N, (E,), device=dev, generator=g)
+out = torch.zeros(N, K, device=dev)
+res['scatter_max_atomic_fresh_E32000_K64'] = dict(ms=round(timeit(lambda: ops.scatter_max(src, index, 0, None, N), n=30), 4))
+res['scatter_max_atomic_out_E32000_K64'] = dict(ms=round(timeit(lambda: ops.scatter_max(src, index, 0, out, N), n=30), 4))
+src = torch.randn(2_000_000, 16, device=dev, generator=g)
+index = torch.randint(0, 200_000, (2_000_000, 16), device=dev, generator=g)
+res['scatter_max_elementwise_E2M_K16'] = dict(ms=round(timeit(lambda: ops.scatter_max(src, index, 0, None, 200_000)), 4))
+del src, index, out
 for k, v in res.items():
     print(k, json.dumps(v))
