@@ -213,6 +213,18 @@ def hetero_neighbor_sample(node_types, edge_types, rowptr_dict, col_dict, seed_d
     `rng_seed` plays the role of torch.manual_seed(seed) right before the call; `fill(buf128)`
     optionally replaces the word source.
     """
+    # the reference's argument checks (neighbor_kernel.cpp:541-546, :571) ...
+    if (node_time_dict is not None or edge_time_dict is not None) and not disjoint:
+        raise RuntimeError('Temporal sampling needs to create disjoint subgraphs')
+    if node_time_dict is not None and edge_time_dict is not None:
+        raise RuntimeError('Only one of node-level or edge-level sampling is supported')
+    if edge_time_dict is not None and seed_time_dict is None:
+        raise RuntimeError('Seed time needs to be specified')
+    # ... and its `node_time_dict.value().at(seed type)` (:692), which throws for a seed type that has no time at all
+    if node_time_dict is not None or edge_time_dict is not None:
+        for k, s in seed_dict.items():
+            if not (seed_time_dict and k in seed_time_dict) and not (node_time_dict and k in node_time_dict):
+                raise RuntimeError('Seed time needs to be specified')
     nt_index = {t: i for i, t in enumerate(node_types)}
     E = len(edge_types)
     et_src = np.array([nt_index[e[0]] for e in edge_types], dtype=np.int32)

@@ -682,6 +682,7 @@ oracle_result* oracle_hetero_neighbor_sample_w(
         mapper_insert(&n->map, batch_idx, seed[si][i], &ins);
         if (seed_time && seed_time[si]) vpush(&seed_times, seed_time[si][i]);
         else if (node_time && node_time[t]) vpush(&seed_times, node_time[t][seed[si][i]]);
+        else vpush(&seed_times, 0); /* a temporal call never gets here: the wrapper raises where the reference's .at() throws (:692) */
         batch_idx++;
       }
     }

@@ -295,3 +295,48 @@ def test_reduce_ops_on_cpu_autograd_and_composites():
     assert torch.isfinite(x.grad).all()
     with pytest.raises(RuntimeError):
         ops.scatter_sum(src.detach(), torch.tensor([9] * 50), 0, None, 7)   # out-of-range index: checked on CPU
+
+
+# ---- heterogeneous temporal sampling on CPU tensors ----------------------------------------------------------------------
+# pyg_binding_cpu.cpp has its own implementation of the drivers; a subset of the grid of
+# tests/test_sampler_hetero_temporal_gpu.py against the oracle (bit for bit, generator state included), and the draw-free
+# cases against the plain numpy reference of tests/_temporal_ref.py.
+
+from tests import _temporal_ref as TR  # noqa: E402
+
+
+@pytest.mark.parametrize('level,strategy,replace,csc,partial,fanouts',
+                         [('node', 'uniform', False, True, True, 'synchronising'), ('node', 'last', True, False, True, 'fused'),
+                          ('node', 'last', False, True, False, 'synchronising'), ('edge', 'uniform', True, True, True, 'queued'),
+                          ('edge', 'last', False, True, True, 'synchronising'), ('edge', 'uniform', False, False, False, 'fused')])
+def test_hetero_temporal_grid_matches_oracle_on_cpu(level, strategy, replace, csc, partial, fanouts):
+    # (`fanouts`: the three sets of the GPU grid, named after the HIP driver they select there)
+    g, col, fan, kw = TR.grid_case(level, partial, csc, strategy, replace, fanouts=fanouts)
+    out, after, ref = TR.run_both(sampler, t, g, col, fan, kw, 31)
+    TR.assert_same(out, after, ref, 31, g)
+    assert sum(sum(v) for v in ref[5].values()) > 10_000
+    if strategy == 'last' and not replace and not partial:
+        assert ref[6]['rng_draws'] == 0
+    else:
+        assert ref[6]['rng_blocks'] > 3
+    # int32 graph, int64 times: same samples, same generator advance, int32 outputs
+    torch.manual_seed(31)
+    o32 = TR.sample_with(sampler, t, g, col, fan, kw, index=torch.int32)
+    assert int(torch.randint(TR.I64_MIN, TR.I64_MAX, (1,)).item()) == after
+    for i in range(4):
+        for k, v in o32[i].items():
+            assert v.dtype == torch.int32 and torch.equal(v.long(), out[i][k])
+
+
+@pytest.mark.parametrize('index', range(len(TR.DRAW_FREE_CASES)), ids=[TR.draw_free_id(c) for c in TR.DRAW_FREE_CASES])
+def test_hetero_temporal_draw_free_cases_match_numpy_reference_on_cpu(index):
+    g, col, fan, kw = TR.draw_free_case(TR.DRAW_FREE_CASES[index], index)
+    out = TR.sample_with(sampler, t, g, col, fan, kw)
+    TR.assert_matches_reference(out, TR.draw_free_reference(g, col, fan, kw), g.edge_types, kw['csc'])
+
+
+def test_hetero_temporal_errors_on_cpu():
+    def sample(node_types, edge_types, rowptr, col, seeds, fan, **kw):
+        tkw = {k: (TR.to_tensors(v, t) if isinstance(v, dict) else v) for k, v in kw.items()}
+        return sampler.hetero_neighbor_sample(TR.to_tensors(rowptr, t), TR.to_tensors(col, t), TR.to_tensors(seeds, t), fan, **tkw)
+    TR.check_temporal_errors(sample)

@@ -1,6 +1,8 @@
 """Differential fuzzing of the HIP sampler against the oracle: random homogeneous / heterogeneous graphs,
 fan-outs (incl. 0, -1, > 64), duplicate seeds, replace / disjoint / temporal / biased (edge_weight) modes, int32
-graphs; every output and the generator state must match bit for bit.    python tools/fuzz_sampler.py [cases] [seed]"""
+graphs; heterogeneous temporal cases (node or edge level, full or partial time dictionaries, both strategies, seed times
+given or derived); every output and the generator state must match bit for bit.
+python tools/fuzz_sampler.py [cases] [seed]"""
 import os, sys, time
 import numpy as np
 import torch
@@ -9,6 +11,7 @@ import oracle
 from pyg_lib_amd import sampler
 I64_MIN, I64_MAX = -2 ** 63, 2 ** 63 - 1
 dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+LAST = {}  # the counts of the last run(): cases, hetero, temporal, biased, hetero_temporal
 def run(cases=200, seed=0):
     rng = np.random.default_rng(seed)
 
@@ -41,7 +44,7 @@ def run(cases=200, seed=0):
 
 
     t0 = time.time()
-    nh = nt = nb = 0
+    nh = nt = nb = nht = 0
     for it in range(cases):
         seed = int(rng.integers(0, 2 ** 31))
         replace, disjoint = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
@@ -115,13 +118,46 @@ def run(cases=200, seed=0):
                 if replace:  # at::multinomial: every sampled row needs a positive weight
                     wd = {e: np.abs(v) + v.dtype.type(0.25) for e, v in wd.items()}
                 nb += 1
+            # temporal modes: every choice comes from a second generator derived from the case seed, so the graphs and modes of
+            # the other cases stay what they were before these existed
+            rng2 = np.random.default_rng([seed, 1])
+            tkw = {}
+            if wd is None and rng2.random() < 0.4:  # never together with edge_weight_dict (neighbor_kernel.cpp:579-582)
+                disjoint = True
+                node_level, partial = bool(rng2.integers(0, 2)), bool(rng2.integers(0, 2))
+                tkw['temporal_strategy'] = str(rng2.choice(['uniform', 'last']))
+                explicit = not node_level or bool(rng2.integers(0, 2))  # seed_time_dict present, or derived from node_time_dict
+                if node_level:
+                    known = [t for t in types if t in seeds or any(t in (e[0], e[2]) for e in ets)]  # (the wrapper's node types)
+                    ntd = {t: rng2.integers(0, 50, sizes[t], dtype=np.int64) for t in known}
+                    if partial:  # a type without a time: the relations into it are sampled untimed
+                        keep = [t for t in known if (not explicit and t in seeds) or rng2.random() < 0.6] or [known[0]]
+                        ntd = {t: ntd[t] for t in keep}
+                    for e in ets:
+                        if e[2] in ntd:
+                            rowid = np.repeat(np.arange(sizes[e[0]]), np.diff(rp[e]))
+                            cl[e] = cl[e][np.lexsort((ntd[e[2]][cl[e]], rowid))]
+                    tkw['node_time_dict'] = ntd
+                else:
+                    etd = {}
+                    for e in ets:
+                        et_ = rng2.integers(0, 50, cl[e].size, dtype=np.int64)
+                        etd[e] = et_[np.lexsort((et_, np.repeat(np.arange(sizes[e[0]]), np.diff(rp[e]))))]
+                    if partial:
+                        keep = [e for e in ets if rng2.random() < 0.6] or [ets[0]]
+                        etd = {e: etd[e] for e in keep}
+                    tkw['edge_time_dict'] = etd
+                if explicit:
+                    tkw['seed_time_dict'] = {t: rng2.integers(0, 60, v.size, dtype=np.int64) for t, v in seeds.items()}
+                nht += 1
+            dkw = {k: ({a: dev(b) for a, b in v.items()} if isinstance(v, dict) else v) for k, v in tkw.items()}
             torch.manual_seed(seed)
             out = sampler.hetero_neighbor_sample({e: dev(v) for e, v in rp.items()}, {e: dev(v) for e, v in cl.items()},
                                                  {k: dev(v) for k, v in seeds.items()}, fan, replace=replace, disjoint=disjoint,
-                                                 edge_weight_dict=None if wd is None else {e: dev(v) for e, v in wd.items()})
+                                                 edge_weight_dict=None if wd is None else {e: dev(v) for e, v in wd.items()}, **dkw)
             after = int(torch.randint(I64_MIN, I64_MAX, (1,)).item())
             ref = oracle.hetero_neighbor_sample(types, ets, rp, cl, seeds, fan, replace=replace, disjoint=disjoint, rng_seed=seed,
-                                                edge_weight_dict=wd)
+                                                edge_weight_dict=wd, **tkw)
             ok = True
             for e in ets:
                 ok = ok and torch.equal(out[0][e].cpu(), torch.from_numpy(ref[0][e])) and torch.equal(out[1][e].cpu(), torch.from_numpy(ref[1][e]))
@@ -137,7 +173,9 @@ def run(cases=200, seed=0):
         if not ok:
             print('MISMATCH at case', it, 'seed', seed, 'replace', replace, 'disjoint', disjoint, 'L', L)
             return False
-    print(f'{cases} cases ({nh} hetero, {nt} temporal, {nb} biased) match the oracle bit for bit in {time.time() - t0:.1f}s')
+    LAST.update(cases=cases, hetero=nh, temporal=nt, biased=nb, hetero_temporal=nht)
+    print(f'{cases} cases ({nh} hetero, {nt} temporal, {nht} hetero temporal, {nb} biased) match the oracle bit for bit '
+          f'in {time.time() - t0:.1f}s')
     return True
 
 
