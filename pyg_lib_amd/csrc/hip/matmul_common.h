@@ -1,8 +1,13 @@
-// Element types, the device-side group descriptor and the MFMA / rounding helpers shared by the translation units of
-// segment_matmul / grouped_matmul (matmul.hip: shape-specialised kernels + dispatch, matmul_gen.hip: general shapes).
+// Element types, the device-side group descriptor and the MFMA / rounding / packing helpers shared by the translation
+// units of segment_matmul / grouped_matmul, and the launch functions through which matmul.hip (tile tables, route choice,
+// entry points) reaches the kernel families: matmul_lds.hip (W in LDS, contiguous tile ranges), matmul_f32_pipe.hip
+// (fp32 K = 128), matmul_k128.hip (16-bit K = M = 128: cyclic / ticket schedules), matmul_k256.hip (16-bit K = 256, 256
+// columns per workgroup), matmul_ring.hip (item rings), matmul_gen.hip (general shapes).
 #pragma once
 
 #include "common.h"
+
+#include <algorithm>
 
 namespace pyg_hip {
 namespace {
@@ -12,6 +17,10 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTileRows = 128;  // rows per workgroup tile in the MFMA kernels (4 waves x 32)
+constexpr int kPairRows = 64;   // rows per tile of the ticket kernel (2 waves x 32)
+constexpr int kTicketWords = 256;  // 8 per-XCD tile counters, 128 bytes apart
 
 struct bf16_t {
   uint16_t v;
@@ -82,7 +91,75 @@ __device__ __forceinline__ float round_to(bf16_t, float v) { return (float)(__bf
 __device__ __forceinline__ float round_to(f16_t, float v) { return (float)(_Float16)v; }
 __device__ __forceinline__ float round_to(float, float v) { return v; }
 
-// Split-bf16 helpers (fp32 K = M-chunk = 128 kernel, FLAGS bit 2).  split2(a, b): round-to-nearest-even bf16 pair of
+// Store 16 consecutive output elements (fp32 accumulators -> T) at `dst` (16-byte aligned).
+__device__ __forceinline__ void store16(bf16_t*, char* dst, const float (&v)[16]) {
+  u32x4 lo, hi;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint16_t a = __builtin_bit_cast(uint16_t, (__bf16)v[2 * i]);
+    uint16_t b = __builtin_bit_cast(uint16_t, (__bf16)v[2 * i + 1]);
+    lo[i] = (uint32_t)a | ((uint32_t)b << 16);
+    uint16_t c = __builtin_bit_cast(uint16_t, (__bf16)v[8 + 2 * i]);
+    uint16_t d = __builtin_bit_cast(uint16_t, (__bf16)v[8 + 2 * i + 1]);
+    hi[i] = (uint32_t)c | ((uint32_t)d << 16);
+  }
+  reinterpret_cast<u32x4*>(dst)[0] = lo;
+  reinterpret_cast<u32x4*>(dst)[1] = hi;
+}
+__device__ __forceinline__ void store16(f16_t*, char* dst, const float (&v)[16]) {
+  u32x4 lo, hi;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint16_t a = __builtin_bit_cast(uint16_t, (_Float16)v[2 * i]);
+    uint16_t b = __builtin_bit_cast(uint16_t, (_Float16)v[2 * i + 1]);
+    lo[i] = (uint32_t)a | ((uint32_t)b << 16);
+    uint16_t c = __builtin_bit_cast(uint16_t, (_Float16)v[8 + 2 * i]);
+    uint16_t d = __builtin_bit_cast(uint16_t, (_Float16)v[8 + 2 * i + 1]);
+    hi[i] = (uint32_t)c | ((uint32_t)d << 16);
+  }
+  reinterpret_cast<u32x4*>(dst)[0] = lo;
+  reinterpret_cast<u32x4*>(dst)[1] = hi;
+}
+__device__ __forceinline__ void store16(float*, char* dst, const float (&v)[16]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f32x4 q = {v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]};
+    reinterpret_cast<f32x4*>(dst)[i] = q;
+  }
+}
+
+// One 16-byte chunk of T from fp32 values: pack8 = 8 values of a 16-bit type, pack_chunk = 8 of those or 4 fp32.
+__device__ __forceinline__ u32x4 pack8(bf16_t, const float* v) {
+  u32x4 o;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint16_t a = __builtin_bit_cast(uint16_t, (__bf16)v[2 * i]);
+    uint16_t b = __builtin_bit_cast(uint16_t, (__bf16)v[2 * i + 1]);
+    o[i] = (uint32_t)a | ((uint32_t)b << 16);
+  }
+  return o;
+}
+__device__ __forceinline__ u32x4 pack8(f16_t, const float* v) {
+  u32x4 o;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint16_t a = __builtin_bit_cast(uint16_t, (_Float16)v[2 * i]);
+    uint16_t b = __builtin_bit_cast(uint16_t, (_Float16)v[2 * i + 1]);
+    o[i] = (uint32_t)a | ((uint32_t)b << 16);
+  }
+  return o;
+}
+
+__device__ __forceinline__ u32x4 pack_chunk(bf16_t t, const float* v) { return pack8(t, v); }
+__device__ __forceinline__ u32x4 pack_chunk(f16_t t, const float* v) { return pack8(t, v); }
+__device__ __forceinline__ u32x4 pack_chunk(float, const float* v) {
+  u32x4 o;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) o[i] = __builtin_bit_cast(uint32_t, v[i]);
+  return o;
+}
+
+// Split-bf16 helpers (fp32 K = M-chunk = 128 kernels).  split2(a, b): round-to-nearest-even bf16 pair of
 // (a, b) packed {a low, b high} (v_cvt_pk_bf16_f32), and the exact fp32 residuals a - bf16(a), b - bf16(b).
 typedef __bf16 bf16x2_hw __attribute__((ext_vector_type(2)));
 typedef float f32x2_hw __attribute__((ext_vector_type(2)));
@@ -114,8 +191,38 @@ __host__ __device__ inline int gen_class(const void* a, const void* w, const voi
   return lx | (lw << 3) | (lc << 6);
 }
 
+// Grid of a persistent tile-walking kernel: one workgroup per tile, at most `per_cu` per compute unit.  With `ncol` > 1
+// column-chunk workgroups per tile range the ranges come in whole octets (workgroup ids 8 apart = same XCD, see the
+// kernels' decode) and the chip's resident workgroup count is kept.
+inline unsigned tile_grid(int64_t tiles_upper, int per_cu, int ncol = 1) {
+  const int64_t resident = (int64_t)device_info().num_cus * per_cu;
+  int64_t gx = std::min<int64_t>(std::max<int64_t>(tiles_upper, 1), resident);
+  if (ncol > 1) gx = std::max<int64_t>(8, (std::min<int64_t>(gx, resident / ncol) + 7) / 8 * 8);
+  return (unsigned)(gx * ncol);
+}
+
 }  // namespace
 
+// The launch functions below take the device descriptors, the tile prefix their kernel walks (`tile_start`: 128-row
+// tiles, `tile_start2`: 256-row, `tile_start3`: 64-row), the number of groups, an upper bound of the tile count and the
+// stream; each owns its kernel's LDS size, block size and grid.  `dtype` is PYG_F32 / PYG_BF16 / PYG_F16.
+// matmul_lds.hip: W^T in LDS, one contiguous tile range per workgroup, M / MC column chunks; the (K, MC) pairs of its
+// instantiation list, anything else is PYG_HIP_ERR_INVALID.  launch_lds_f32x3: fp32 K = 128, MC = 128 in split-bf16.
+int launch_lds(int dtype, int K, int MC, const void* descs, const int32_t* tile_start, int B, int64_t tiles_upper, int M,
+               hipStream_t stream);
+int launch_lds_f32x3(const void* descs, const int32_t* tile_start, int B, int64_t tiles_upper, int M, hipStream_t stream);
+// matmul_f32_pipe.hip: fp32 K = 128, MC = 32 / 64 / 128, epilogue overlapped with the next tile's MFMAs.
+int launch_f32_pipe(int MC, const void* descs, const int32_t* tile_start, int B, int64_t tiles_upper, int M,
+                    hipStream_t stream);
+// matmul_k128.hip: 16-bit K = M = 128.  `tickets`: kTicketWords zeroed counters.
+int launch_k128_cyc(int dtype, const void* descs, const int32_t* tile_start2, int B, int64_t tiles2_upper, hipStream_t stream);
+int launch_k128_ticket(int dtype, const void* descs, const int32_t* tile_start3, int B, int64_t tiles3_upper,
+                       unsigned int* tickets, hipStream_t stream);
+// matmul_k256.hip: 16-bit K = 256, 256 columns per workgroup (M % 256 == 0; the 64-rows-per-wave form: M == 256).
+int launch_k256_wide(int dtype, const void* descs, const int32_t* tile_start, int B, int64_t tiles_upper, int M,
+                     hipStream_t stream);
+int launch_k256_wide_r2(int dtype, const void* descs, const int32_t* tile_start2, int B, int64_t tiles2_upper,
+                        hipStream_t stream);
 // matmul_gen.hip: the general-shape MFMA kernel (per-group K, M and alignment class).  `dtype` is PYG_F32 / PYG_BF16 /
 // PYG_F16; `tile_start` the prefix of 128-row tiles per group, `mean_k` the row-weighted mean contraction length.
 int launch_matmul_gen(int dtype, const void* descs, const int32_t* tile_start, int B, int64_t tiles_upper, int64_t mean_k,

@@ -1,8 +1,8 @@
-// General-shape MFMA kernel of segment_matmul / grouped_matmul (own translation unit; dispatch in matmul.hip).
+// General-shape MFMA kernel of segment_matmul / grouped_matmul (own translation unit; route choice in matmul.hip).
 //
 // The reference's CUDA path hands CUTLASS one GemmCoord per group (pyg_lib/csrc/ops/cuda/matmul_kernel.cu:33-67), i.e.
 // every group has its own (rows, K, M); its tests use K = 16 / 9 / 32 with M = 48 / 42 / 64
-// (test/ops/test_matmul.py:56-72).  The specialised kernels of matmul.hip cover ONE (K, M) per launch with
+// (test/ops/test_matmul.py:56-72).  The specialised kernels (matmul_lds.hip and its siblings) cover ONE (K, M) per launch with
 // K in {32 ... 512}, M % 32 == 0 and 16-byte aligned rows; everything else -- K = 100 (ogbn-products), the K-per-type
 // lists of a HeteroDictLinear, odd M, element-aligned views -- runs here:
 //   * one workgroup (4 waves) per 128-row tile of ONE group, dispatched in address order (run-to-completion grid, the

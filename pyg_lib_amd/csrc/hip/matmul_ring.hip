@@ -1,8 +1,8 @@
 // Item-ring kernels of segment_matmul / grouped_matmul: a relation's W lives in REGISTERS (each wave of a four-wave
 // workgroup a column slice), LDS is a ring of 16 KiB slots filled by LDS-DMA that carries X tiles and -- on a relation
 // change -- the chunks of the new W, which have the shape of an X tile.  Three instances: 16-bit K = M = 256 (the C4
-// shape), 16-bit K = M = 128 for many short relations, fp32 K = M = 128 through split-bf16 MFMAs.  Dispatch, tile
-// tables and the other kernels: matmul.hip.
+// shape), 16-bit K = M = 128 for many short relations, fp32 K = M = 128 through split-bf16 MFMAs.  Tile tables
+// and the route choice: matmul.hip; the other kernel families: matmul_lds.hip, matmul_k128.hip, matmul_k256.hip.
 #include "matmul_common.h"
 
 #include <algorithm>

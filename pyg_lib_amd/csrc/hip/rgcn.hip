@@ -14,7 +14,7 @@
 //     256-byte row per 16 lanes -- into registers one tile ahead, and parks them in the same XOR-swizzled per-wave
 //     stage the segment_matmul kernels use;
 //   * W_r is copied in its native [K][M] layout by LDS-DMA and read through ds_read_b64_tr_b16 (see
-//     mfma_rows_cyc_kernel in matmul.hip for the block permutation that keeps those reads conflict free);
+//     mfma_rows_cyc_kernel in matmul_k128.hip for the block permutation that keeps those reads conflict free);
 //   * epilogue = SCATTER: the 32 x 128 messages of a wave are rounded to the storage type (exactly what the
 //     unfused chain materialises), parked in the stage, and every lane walks its two columns down the 32 rows,
 //     summing runs of equal destination in fp32 -- the sampler emits a relation's edges grouped by source node, so

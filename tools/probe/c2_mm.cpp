@@ -1,7 +1,8 @@
 // Probe (not product): times pyg_hip_segment_matmul on the C2 shape straight through the C-ABI (no torch),
 // once per environment setting given on the command line.
 //   hipcc --offload-arch=gfx950 -O2 tools/probe/c2_mm.cpp -o tools/probe/c2_mm -Iinclude -Lpyg_lib_amd -lpyg_hip -Wl,-rpath,'$ORIGIN/../../pyg_lib_amd'
-//   tools/probe/c2_mm [rows] [K] [M] [B] -- "" "PYG_HIP_MM_WGS=1" "PYG_HIP_MM_CHUNK=8" ...
+//   tools/probe/c2_mm [rows] [K] [M] [B] -- "" "NAME=value[,NAME=value]" ...
+// (settings of the HIP runtime: the matmul kernels themselves read no environment variable)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
