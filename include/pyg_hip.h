@@ -57,6 +57,7 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  10: pyg_hip_sampled_op, pyg_hip_sampled_op_backward (fused gather + binary operator and its per-edge gradients).
  *   9: pyg_hip_random_walk, pyg_hip_subgraph (added after the original hot-path contract).
  *   8: round 6 -- pyg_hip_segment_csr_ws / pyg_hip_gather_csr_ws / pyg_hip_csr_hub_workspace_size (scratch for hub rows);
  *      pyg_hip_scatter uses the dead parts of its workspace for the same purpose (no change for its callers).
@@ -67,7 +68,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 9
+#define PYG_HIP_ABI_VERSION 10
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -708,6 +709,51 @@ PYG_HIP_API int pyg_hip_fill_reduce_identity(int op, int dtype, void* out, int64
  */
 PYG_HIP_API int pyg_hip_gather_coo(int dtype, const void* src, const int64_t* index, void* out,
                                    int64_t B, int64_t E, int64_t K, int64_t N, void* stream);
+
+/* ---- sampled_op ----------------------------------------------------------------------------- */
+
+typedef enum {
+  PYG_SAMPLED_ADD = 0,
+  PYG_SAMPLED_SUB = 1,
+  PYG_SAMPLED_MUL = 2,
+  PYG_SAMPLED_DIV = 3
+} pyg_sampled_fn;
+
+/*
+ * out[e, :] = left[li(e), :]  (fn)  right[ri(e), :]     for e in [0, E);  li(e) = left_index ? left_index[e] : e, ri alike.
+ * Replaces pyg::sampled_op (schema pyg_lib/csrc/ops/sampled.cpp:57-59; CPU kernel ops/cpu/sampled_kernel.cpp:17-46 =
+ * index_select + operator; CUDA kernel ops/cuda/sampled_kernel.cu:21-106, int64 indices only): the gathered operands
+ * left[left_index] and right[right_index] never exist in memory.
+ *   left [left_rows, F], right [right_rows, F], out [E, F], row-major, all `dtype`.
+ *   index_dtype  PYG_I64 or PYG_I32, the type of BOTH index vectors (E entries each; NULL = the identity, then the table
+ *                has at least E rows).
+ *   Floating dtypes take all four operators; bf16 / fp16 compute in fp32 and round once to nearest-even (torch's CPU
+ *   kernels: same bits, Inf / NaN / signed zeros / denormals included; the division is the correctly rounded one).
+ *   Integer dtypes take add / sub / mul with wrap-around; PYG_SAMPLED_DIV on them returns PYG_HIP_ERR_UNSUPPORTED without a
+ *   launch (the reference's backends disagree there -- true division on the CPU, truncation in CUDA -- and a zero divisor
+ *   must not reach the device).
+ *   Indices are NOT validated on the device (as pyg_hip_gather_coo and the reference's CUDA kernel): an index outside
+ *   [0, left_rows) / [0, right_rows) is an out-of-bounds read; left_rows / right_rows only serve the identity check above.
+ *   E == 0 or F == 0: PYG_HIP_OK without a launch.  Never synchronises.
+ */
+PYG_HIP_API int pyg_hip_sampled_op(int fn, int dtype, const void* left, int64_t left_rows, const void* right,
+                                   int64_t right_rows, int index_dtype, const void* left_index, const void* right_index,
+                                   void* out, int64_t E, int64_t F, void* stream);
+
+/*
+ * Per-edge gradients of pyg_hip_sampled_op for PYG_SAMPLED_MUL / PYG_SAMPLED_DIV, floating dtypes only (add / sub need none:
+ * their edge gradient is grad_out itself).  With g = grad_out[e], a = left[li(e)], b = right[ri(e)] -- each read once --
+ *   mul:  edge_grad_left = g * b      edge_grad_right = g * a
+ *   div:  edge_grad_left = g / b      edge_grad_right = (-g) * ((a / b) / b)
+ * in that operation order (SampledOp::backward, pyg_lib/csrc/ops/autograd/sampled_kernel.cpp:55-82), in opmath (fp32 for
+ * the 16-bit types) with ONE rounding on store -- the reference rounds every intermediate to `dtype`.  Either output may
+ * be NULL (not wanted); both are [E, F].  The sum over the edges of a node (the reference's index_select_backward) is
+ * the caller's: pyg_hip_scatter.  Indices are not validated, as above.
+ */
+PYG_HIP_API int pyg_hip_sampled_op_backward(int fn, int dtype, const void* grad_out, const void* left, int64_t left_rows,
+                                            const void* right, int64_t right_rows, int index_dtype,
+                                            const void* left_index, const void* right_index, void* edge_grad_left,
+                                            void* edge_grad_right, int64_t E, int64_t F, void* stream);
 
 /* ---- measurement hooks (bench.py) --------------------------------------------------------- */
 

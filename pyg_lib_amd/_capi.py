@@ -12,7 +12,7 @@ _HERE = osp.dirname(osp.abspath(__file__))
 _LIB = None
 
 OK = 0
-ABI_VERSION = 9  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
+ABI_VERSION = 10  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
 DTYPES = {
     torch.float32: 0,
     torch.float64: 1,
@@ -70,6 +70,16 @@ def lib() -> ctypes.CDLL:
         L.pyg_hip_rgcn_pending_error.restype = c.c_int
         L.pyg_hip_atomic_selftest.restype = c.c_int
         L.pyg_hip_atomic_selftest.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_char_p, c.c_size_t, c.c_void_p]
+        # (fn, dtype, left, left_rows, right, right_rows, index_dtype, left_index, right_index, out, E, F, stream)
+        L.pyg_hip_sampled_op.restype = c.c_int
+        L.pyg_hip_sampled_op.argtypes = [c.c_int, c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int, c.c_void_p,
+                                         c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p]
+        # (fn, dtype, grad_out, left, left_rows, right, right_rows, index_dtype, left_index, right_index, edge_grad_left,
+        #  edge_grad_right, E, F, stream)
+        L.pyg_hip_sampled_op_backward.restype = c.c_int
+        L.pyg_hip_sampled_op_backward.argtypes = [c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64,
+                                                  c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64,
+                                                  c.c_int64, c.c_void_p]
         _LIB = L
     return _LIB
 

@@ -93,6 +93,62 @@ def grouped_matmul(
 
 
 # ---------------------------------------------------------------------------------------------------
+# sampled_add / sub / mul / div  (pyg_lib/ops/__init__.py:175-292)
+# ---------------------------------------------------------------------------------------------------
+
+def sampled_add(
+    left: Tensor,
+    right: Tensor,
+    left_index: Optional[Tensor] = None,
+    right_index: Optional[Tensor] = None,
+) -> Tensor:
+    r"""Edge-level sum of two node tensors: ``out[e] = left[left_index[e]] + right[right_index[e]]``, computed in
+    one pass so that neither gathered operand is written to memory (three row passes instead of seven).
+
+    :obj:`left` and :obj:`right` are contiguous ``[N_left, F]`` / ``[N_right, F]`` tensors of one dtype and device.
+    An index is a contiguous 1-D int64 or int32 tensor of ``E`` row numbers; :obj:`None` reads its tensor row by row
+    (which then must have ``E`` rows).  Returns ``[E, F]``.  Differentiable in :obj:`left` and :obj:`right`: the
+    gradient of an indexed side is summed per row through :func:`scatter_sum`, so it is reproducible on large
+    inputs and follows ``torch.use_deterministic_algorithms``.  On a HIP device the indices are not range-checked.
+    """
+    return torch.ops.pyg.sampled_op(left, right, left_index, right_index, 'add')
+
+
+def sampled_sub(
+    left: Tensor,
+    right: Tensor,
+    left_index: Optional[Tensor] = None,
+    right_index: Optional[Tensor] = None,
+) -> Tensor:
+    r"""Edge-level difference ``out[e] = left[left_index[e]] - right[right_index[e]]`` in one pass; arguments,
+    result and gradients as for :func:`sampled_add`."""
+    return torch.ops.pyg.sampled_op(left, right, left_index, right_index, 'sub')
+
+
+def sampled_mul(
+    left: Tensor,
+    right: Tensor,
+    left_index: Optional[Tensor] = None,
+    right_index: Optional[Tensor] = None,
+) -> Tensor:
+    r"""Edge-level product ``out[e] = left[left_index[e]] * right[right_index[e]]`` in one pass; arguments, result
+    and gradients as for :func:`sampled_add`."""
+    return torch.ops.pyg.sampled_op(left, right, left_index, right_index, 'mul')
+
+
+def sampled_div(
+    left: Tensor,
+    right: Tensor,
+    left_index: Optional[Tensor] = None,
+    right_index: Optional[Tensor] = None,
+) -> Tensor:
+    r"""Edge-level quotient ``out[e] = left[left_index[e]] / right[right_index[e]]`` in one pass (true division,
+    correctly rounded); arguments, result and gradients as for :func:`sampled_add`.  Floating-point tensors only on
+    a HIP device: integer division raises there."""
+    return torch.ops.pyg.sampled_op(left, right, left_index, right_index, 'div')
+
+
+# ---------------------------------------------------------------------------------------------------
 # index_sort
 # ---------------------------------------------------------------------------------------------------
 
@@ -403,6 +459,10 @@ def matmul_f32_split(on: bool = True):
 __all__ = [
     'grouped_matmul',
     'segment_matmul',
+    'sampled_add',
+    'sampled_sub',
+    'sampled_mul',
+    'sampled_div',
     'index_sort',
     'scatter',
     'scatter_sum',
