@@ -57,6 +57,7 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  11: pyg_hip_fused_scatter_reduce, its _workspace_size and _backward (sum / mean / min / max in one sort and one pass).
  *  10: pyg_hip_sampled_op, pyg_hip_sampled_op_backward (fused gather + binary operator and its per-edge gradients).
  *   9: pyg_hip_random_walk, pyg_hip_subgraph (added after the original hot-path contract).
  *   8: round 6 -- pyg_hip_segment_csr_ws / pyg_hip_gather_csr_ws / pyg_hip_csr_hub_workspace_size (scratch for hub rows);
@@ -68,7 +69,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 10
+#define PYG_HIP_ABI_VERSION 11
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -754,6 +755,65 @@ PYG_HIP_API int pyg_hip_sampled_op_backward(int fn, int dtype, const void* grad_
                                             const void* right, int64_t right_rows, int index_dtype,
                                             const void* left_index, const void* right_index, void* edge_grad_left,
                                             void* edge_grad_right, int64_t E, int64_t F, void* stream);
+
+/* ---- fused_scatter_reduce ------------------------------------------------------------------- */
+
+typedef enum {
+  PYG_FUSED_SUM = 0,
+  PYG_FUSED_MEAN = 1,
+  PYG_FUSED_MIN = 2,
+  PYG_FUSED_MAX = 3
+} pyg_fused_reduce;
+
+/*
+ * out[n, k * F + f] = reduce_{ops[k]} over { src[e, f] : index[e] == n }      for k in [0, n_ops), n in [0, N)
+ * Replaces pyg_lib.ops.scatter_reduce.fused_scatter_reduce (pyg_lib/ops/scatter_reduce.py:95-181, a Triton kernel: float
+ * atomics, no backward) and four separate pyg_hip_scatter calls on the same index: ONE stable index sort, ONE pass over the
+ * rows with a sum, a min and a max accumulator per element, the count from the row offsets.  No float atomics: the same bits
+ * on every run.
+ *   src [E, F] row-major, floating `dtype` only (PYG_F32 / F64 / F16 / BF16; others: PYG_HIP_ERR_UNSUPPORTED);
+ *   index [E] int64; out [N, n_ops * F] row-major, every element written (need not be cleared).
+ *   ops       n_ops = 1 ... 4 distinct codes of pyg_fused_reduce in any order; slice k of an output row holds ops[k].  An
+ *             empty list, an unknown code or a duplicate: PYG_HIP_ERR_INVALID, nothing launched.
+ *   arg_min / arg_max  NULL (not wanted: no position is tracked) or int64 [N, F]: source position of the first element that
+ *             produced the value, or the sentinel E.  Ignored when the reduction is not listed.
+ *   count_out NULL or int64 [N]: entries per bucket.
+ *   workspace pyg_hip_fused_scatter_reduce_workspace_size(dtype, E, N, F) bytes, 8-byte aligned; less is PYG_HIP_ERR_INVALID
+ *             (there is no second path).
+ * A bucket is reduced in SOURCE order in opmath (fp32 for the 16-bit types and float32, fp64 for float64) with one rounding
+ * on store; mean = (opmath sum) / max(count, 1), rounded once.  Buckets split over lanes or hub chunks combine by a fixed
+ * tree (sums then differ from the sequential order by rounding only; min / max and their positions never).  Empty buckets
+ * read 0 in every slice.  Non-finite values and signed zeros as pyg_hip_scatter above (fresh output): strict
+ * compares, a NaN never wins a min / max, a bucket of NaN only (or one that never beats the start value, the type's largest /
+ * lowest finite number) reads 0 with the sentinel; +0 and -0 tie and the first position wins; a NaN, or +Inf with -Inf,
+ * makes sum and mean NaN; a sum of nothing but -0 reads +0.
+ * `index` is NOT validated on the device.  The forward uses it as a sort key only -- an entry outside [0, N) is never turned
+ * into an address, but it is sorted by its low bits and the results of any bucket may then be wrong.
+ * E == 0, F == 0 or N == 0: PYG_HIP_OK, a non-empty output is cleared, `src` and `index` are not touched.  Never synchronises
+ * (N bounds the sort keys: no read-back); capturable in a HIP graph.
+ */
+PYG_HIP_API size_t pyg_hip_fused_scatter_reduce_workspace_size(int dtype, int64_t E, int64_t N, int64_t F);
+PYG_HIP_API int pyg_hip_fused_scatter_reduce(int dtype, const void* src, const int64_t* index, int64_t E, int64_t F, int64_t N,
+                                             const int* ops, int n_ops, void* out, int64_t* arg_min, int64_t* arg_max,
+                                             int64_t* count_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Backward of pyg_hip_fused_scatter_reduce (the reference has none), one pass over the edges, no atomics, every element of
+ * grad_in [E, F] written once:
+ *   grad_in[e, f] = sum over k in list order of
+ *     sum :  g_k[index[e], f]
+ *     mean:  g_k[index[e], f] / max(count[index[e]], 1)
+ *     min :  arg_min[index[e], f] == e ? g_k[index[e], f] : 0          max: likewise with arg_max
+ * g_k = columns [k * F, (k + 1) * F) of grad_out [N, n_ops * F]; accumulated from +0 in opmath, one rounding.  The whole
+ * gradient of a min / max goes to the first-match position, as in pyg::scatter_min / scatter_max.  arg_min / arg_max / count
+ * are what the forward wrote and are required for the reductions listed (else PYG_HIP_ERR_INVALID).  Here index[e] IS an
+ * address: an entry outside [0, N) is an out-of-bounds read.  E == 0 or F == 0: PYG_HIP_OK without a launch.  Never
+ * synchronises.
+ */
+PYG_HIP_API int pyg_hip_fused_scatter_reduce_backward(int dtype, const void* grad_out, const int64_t* index,
+                                                      const int64_t* arg_min, const int64_t* arg_max, const int64_t* count,
+                                                      int64_t E, int64_t F, int64_t N, const int* ops, int n_ops, void* grad_in,
+                                                      void* stream);
 
 /* ---- measurement hooks (bench.py) --------------------------------------------------------- */
 

@@ -12,7 +12,7 @@ _HERE = osp.dirname(osp.abspath(__file__))
 _LIB = None
 
 OK = 0
-ABI_VERSION = 10  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
+ABI_VERSION = 11  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
 DTYPES = {
     torch.float32: 0,
     torch.float64: 1,
@@ -80,6 +80,19 @@ def lib() -> ctypes.CDLL:
         L.pyg_hip_sampled_op_backward.argtypes = [c.c_int, c.c_int, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64,
                                                   c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64,
                                                   c.c_int64, c.c_void_p]
+        # (dtype, E, N, F)
+        L.pyg_hip_fused_scatter_reduce_workspace_size.restype = c.c_size_t
+        L.pyg_hip_fused_scatter_reduce_workspace_size.argtypes = [c.c_int, c.c_int64, c.c_int64, c.c_int64]
+        # (dtype, src, index, E, F, N, ops, n_ops, out, arg_min, arg_max, count_out, workspace, workspace_bytes, stream)
+        L.pyg_hip_fused_scatter_reduce.restype = c.c_int
+        L.pyg_hip_fused_scatter_reduce.argtypes = [c.c_int, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int64,
+                                                   c.POINTER(c.c_int), c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                   c.c_void_p, c.c_size_t, c.c_void_p]
+        # (dtype, grad_out, index, arg_min, arg_max, count, E, F, N, ops, n_ops, grad_in, stream)
+        L.pyg_hip_fused_scatter_reduce_backward.restype = c.c_int
+        L.pyg_hip_fused_scatter_reduce_backward.argtypes = [c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                            c.c_int64, c.c_int64, c.c_int64, c.POINTER(c.c_int), c.c_int,
+                                                            c.c_void_p, c.c_void_p]
         _LIB = L
     return _LIB
 

@@ -149,6 +149,30 @@ def sampled_div(
 
 
 # ---------------------------------------------------------------------------------------------------
+# fused_scatter_reduce  (pyg_lib/ops/scatter_reduce.py:95-181)
+# ---------------------------------------------------------------------------------------------------
+
+def fused_scatter_reduce(inputs: Tensor, index: Tensor, dim_size: int, reduce_list: List[str]) -> Tensor:
+    r"""Several reductions of :obj:`inputs` over one :obj:`index` in one sort and one pass over the rows (multi-aggregation,
+    ``aggr=['sum', 'mean', 'min', 'max']``): ``out[:, i * F:(i + 1) * F]`` holds ``reduce_list[i]``.
+
+    :obj:`inputs` is a contiguous floating-point ``[E, F]`` tensor (float32, float64, bfloat16 or float16), :obj:`index` a
+    contiguous int64 ``[E]`` tensor of bucket numbers in ``[0, dim_size)`` on the same device; :obj:`reduce_list` holds one
+    to four distinct names out of ``'sum'``, ``'mean'``, ``'min'``, ``'max'`` in any order.  Returns
+    ``[dim_size, len(reduce_list) * F]``.
+
+    A bucket is reduced in source order with float32 accumulators (float64 for float64) and rounded once; ``mean`` is that
+    sum divided by ``max(count, 1)``.  Empty buckets give 0 in every slice; a NaN never wins ``min`` / ``max`` and makes
+    ``sum`` / ``mean`` NaN; ``+0`` and ``-0`` tie and the first one stays.  No float atomics: the result is the same on every
+    run and unchanged under ``torch.use_deterministic_algorithms(True)``.  Differentiable in :obj:`inputs`: the gradient of
+    ``min`` / ``max`` goes to the first position that produced the value, as for :func:`scatter_min`.  The positions are
+    computed only when :obj:`inputs` requires grad.  On a HIP device :obj:`index` is not range-checked, the call never
+    synchronises and can be captured in a graph.
+    """
+    return torch.ops.pyg.fused_scatter_reduce(inputs, index, dim_size, list(reduce_list))
+
+
+# ---------------------------------------------------------------------------------------------------
 # index_sort
 # ---------------------------------------------------------------------------------------------------
 
@@ -463,6 +487,7 @@ __all__ = [
     'sampled_sub',
     'sampled_mul',
     'sampled_div',
+    'fused_scatter_reduce',
     'index_sort',
     'scatter',
     'scatter_sum',
