@@ -57,6 +57,7 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  12: pyg_hip_scatter_route, pyg_hip_scatter_last_route (which kernel serves a scatter call: asked without running, told after).
  *  11: pyg_hip_fused_scatter_reduce, its _workspace_size and _backward (sum / mean / min / max in one sort and one pass).
  *  10: pyg_hip_sampled_op, pyg_hip_sampled_op_backward (fused gather + binary operator and its per-edge gradients).
  *   9: pyg_hip_random_walk, pyg_hip_subgraph (added after the original hot-path contract).
@@ -69,7 +70,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 11
+#define PYG_HIP_ABI_VERSION 12
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -664,24 +665,39 @@ typedef enum {
  *             with the reduce identity: empty buckets are then reset to 0
  *             (scatter_kernel.cpp:351-360).  Otherwise out_init points to a copy of the caller's
  *             initial `out` and untouched buckets keep their value.
- *   index_sorted  bit 0 (PYG_HIP_SCATTER_SORTED) promises an ascending index along e (the COO contract): runs are
- *             then reduced without atomics.  Bit 1 (PYG_HIP_SCATTER_FRESH_SUM, SUM only): `out` is a fresh,
- *             UNINITIALISED output -- the sorted path then writes every slot without reading or clearing it (2 x N x K
- *             bytes less traffic), every other path clears it first.
- *   workspace optional scratch of pyg_hip_scatter_workspace_size(B, E, N) bytes; with it, sums and min / max with an
- *             index broadcast along k run atomic-free: buckets become CSR rows (directly for a sorted index, after
- *             a stable index sort for one large unsorted index vector with rows of >= 64 bytes) reduced in SOURCE
- *             order -- deterministic, fp32 accumulation with one rounding per output, every output row written
- *             once; min / max: no CAS loops, no second arg pass, same exact values and first-match arg.  Without it
- *             (and for small or element-wise indexed inputs, float64 sums) the atomic kernels run.
- *             Bit 2 (PYG_HIP_SCATTER_CAS): the atomic kernels add floats / doubles / packed 16-bit pairs through
- *             compare-and-swap loops instead of the hardware's floating-point atomic adds.
- *             Bit 3 (PYG_HIP_SCATTER_DETERMINISTIC, floating SUM): no float atomics at all -- an unsorted index vector
- *             broadcast along k (one vector, B == 1) takes the stable-sort + CSR-row path WHATEVER its size, row width
- *             or floating type (needs the workspace): sums in source order, the same bits in every run, like the
- *             reference's sequential CPU loop (ops/cpu/scatter_kernel.cpp:29-127).  Layouts without an atomic-free
- *             kernel (element-wise indices, B > 1 unsorted) and floating MUL return PYG_HIP_ERR_UNSUPPORTED with the
- *             bit set.  The torch binding sets it when torch.are_deterministic_algorithms_enabled().
+ *   index_sorted  flag bits:
+ *             bit 0 (PYG_HIP_SCATTER_SORTED) promises an ascending index along e (the COO contract).
+ *             Bit 1 (PYG_HIP_SCATTER_FRESH_SUM, SUM only): `out` is a fresh, UNINITIALISED output -- the rows routes
+ *             write every slot without reading or clearing it (2 x N x K bytes less traffic), the other routes clear it.
+ *             Bit 2 (PYG_HIP_SCATTER_CAS): the atomic sums add floats / doubles / packed 16-bit pairs through
+ *             compare-and-swap loops instead of the hardware's floating-point atomic adds (a flavour, not a route).
+ *             Bit 3 (PYG_HIP_SCATTER_DETERMINISTIC): no floating-point atomics -- see the table.  Ignored for integer
+ *             types and for MIN / MAX (exact on every route).  The torch binding sets it when
+ *             torch.are_deterministic_algorithms_enabled().
+ *   workspace optional scratch of pyg_hip_scatter_workspace_size(B, E, N) bytes for the rows routes; NULL, or fewer
+ *             bytes than the route needs (csr_rows: the B x (N + 1) row offsets, a multiple of 256 bytes; sort_rows:
+ *             the full size for B = 1), means "not offered" and the call takes the route it would take without one.
+ *
+ * The route of a call -- the first line that applies (pyg_hip_scatter_route asks, pyg_hip_scatter_last_route tells):
+ *   none          B x E x K == 0
+ *   csr_rows      SUM / MIN / MAX, index broadcast along k (stride_k == 0), SORTED, workspace: buckets are CSR rows
+ *   sort_rows     SUM / MIN / MAX, stride_k == 0, not SORTED, ONE index vector (B == 1, stride_e == 1), workspace, and
+ *                   MIN / MAX:            E >= 2^15
+ *                   SUM f32 / f16 / bf16: E >= 2^15 and rows of >= 64 bytes
+ *                   SUM, DETERMINISTIC:   any E, row width and floating type (float64 included)
+ *                 -- one stable index sort, CSR rows read through the permutation
+ *   unsupported   DETERMINISTIC, floating SUM or MUL: pyg_hip_scatter returns PYG_HIP_ERR_UNSUPPORTED (element-wise
+ *                 indices, B > 1 unsorted, no workspace; floating MUL always)
+ *   atomic        MIN / MAX: integer atomics / a CAS loop on the reference's `<` / `>`, an arg pass, reset of empty buckets
+ *   elem          MUL: CAS loop per element
+ *   vec_sorted / vec_unsorted   SUM f32 / f16 / bf16, stride_k == 0, rows of whole 16-byte slices, src and out 16-byte
+ *                 aligned, and SORTED or more than four slices per row: a thread owns a slice over 32 / 8 positions
+ *   pair          SUM f16 / bf16, stride_k == 0, K even, not SORTED, src and out 4-byte aligned: one packed add per pair
+ *   elem          every other SUM (float64, integers, element-wise indices, ...): one native atomic (8- / 16-bit: a CAS
+ *                 loop) per element
+ * The rows routes reduce every bucket in SOURCE order without atomics: deterministic, the same bits in every run like the
+ * reference's sequential CPU loop (ops/cpu/scatter_kernel.cpp:29-127), fp32 accumulation with one rounding per output,
+ * every output row written once; min / max: no CAS loops, no second arg pass, same exact values and first-match arg.
  * Non-finite values and signed zeros follow the reference's sequential loops on every path: a NaN never
  * wins a min / max (a bucket of NaN only counts as empty) and makes a sum NaN; +0 and -0 tie, the first one seen stays
  * (value bits and arg, also on the atomic path); a sum of nothing but -0 into a caller's -0 stays -0, into a fresh output
@@ -691,7 +707,27 @@ typedef enum {
 #define PYG_HIP_SCATTER_FRESH_SUM 2
 #define PYG_HIP_SCATTER_CAS 4
 #define PYG_HIP_SCATTER_DETERMINISTIC 8
+#define PYG_HIP_SCATTER_ROUTE_NONE 0
+#define PYG_HIP_SCATTER_ROUTE_CSR_ROWS 1
+#define PYG_HIP_SCATTER_ROUTE_SORT_ROWS 2
+#define PYG_HIP_SCATTER_ROUTE_VEC_SORTED 3
+#define PYG_HIP_SCATTER_ROUTE_VEC_UNSORTED 4
+#define PYG_HIP_SCATTER_ROUTE_PAIR 5
+#define PYG_HIP_SCATTER_ROUTE_ELEM 6
+#define PYG_HIP_SCATTER_ROUTE_ATOMIC 7
+#define PYG_HIP_SCATTER_ROUTE_UNSUPPORTED 8
 PYG_HIP_API size_t pyg_hip_scatter_workspace_size(int64_t B, int64_t E, int64_t N);
+/* The table above as a query: the PYG_HIP_SCATTER_ROUTE_* code pyg_hip_scatter would take for these scalar arguments, a
+ * workspace of `workspace_bytes` bytes (0: none) and `misalign` = the low four bits of (src | out), which only decide among
+ * vec_*, pair and elem.  An unknown op or dtype or a negative size answers PYG_HIP_SCATTER_ROUTE_UNSUPPORTED.  Launches
+ * nothing and needs no device: like pyg_hip_scatter_workspace_size it reads the current device's compute-unit count (the
+ * sort's scratch depends on it) and assumes an MI355X where there is none. */
+PYG_HIP_API int pyg_hip_scatter_route(int op, int dtype, int64_t index_stride_b, int64_t index_stride_e,
+                                      int64_t index_stride_k, int64_t B, int64_t E, int64_t K, int64_t N,
+                                      int flags, size_t workspace_bytes, unsigned misalign);
+/* Name of the route ("csr_rows", ... as in the table; "none" for a call that did nothing or failed its argument checks)
+ * the last pyg_hip_scatter call on this thread took: lets tests assert which kernel ran. */
+PYG_HIP_API const char* pyg_hip_scatter_last_route(void);
 PYG_HIP_API int pyg_hip_scatter(int op, int dtype, const void* src, const int64_t* index,
                                 int64_t index_stride_b, int64_t index_stride_e,
                                 int64_t index_stride_k, void* out, int64_t* arg_out,

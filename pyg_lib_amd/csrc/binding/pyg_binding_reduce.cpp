@@ -176,40 +176,32 @@ static std::tuple<Tensor, Tensor> reduce_core(int op, bool coo, const Tensor& sr
     if (minmax && fresh) out.masked_fill_(arg == src_c.size(dim), 0);
     return std::make_tuple(out, arg);
   }
-  // scratch for the sort-based sum (large unsorted float scatters only; see pyg_hip_scatter)
-  Tensor ws;
-  const bool sort_sum = op == OP_SUM && !coo && l.B == 1 && l.isk == 0 && l.ise == 1 && l.E >= (1 << 15) &&
-                        at::isFloatingType(src_c.scalar_type()) && l.K * (int64_t)src_c.element_size() >= 64;
-  // min / max: atomic-free CSR walk for a sorted (COO) index or one large unsorted index vector
-  const bool csr_minmax = minmax && l.isk == 0 && (coo || (l.B == 1 && l.ise == 1 && l.E >= (1 << 15)));
-  const bool csr_sum = op == OP_SUM && coo && l.isk == 0;  // sorted index: atomic-free CSR row sums
+  // Which kernel serves the call is the library's choice (the route table of pyg_hip_scatter in pyg_hip.h); it is asked
+  // first because the atomic-free rows routes need a workspace -- the full size: what lies behind the row offsets is scratch
+  // for hub rows -- and the atomic routes none.  (misalign = 0: the rows routes do not look at the alignment.)
+  const size_t ws_bytes = pyg_hip_scatter_workspace_size(l.B, l.E, l.N);
+  auto route = [&](int flags) { return pyg_hip_scatter_route(op, dt, l.isb, l.ise, l.isk, l.B, l.E, l.K, l.N, flags, ws_bytes, 0); };
   // torch.use_deterministic_algorithms(True): floating sums / products must not go through atomics (their result would
-  // depend on the order the adds land in).  Sums have an atomic-free kernel for a sorted index and for one unsorted index
-  // vector of ANY size (stable sort + CSR rows, source order); where there is none, torch's own convention applies:
-  // alertNotDeterministic raises, or warns under warn_only and the atomic kernel runs.
-  const bool floating = at::isFloatingType(src_c.scalar_type());
-  // (tl_prefer_sorted_sum: scatter_mean's bucket sizes -- see ScatterMean -- ask for the same path without the mode)
-  const bool prefer_sorted = tl_prefer_sorted_sum && op == OP_SUM && floating && !coo && l.B == 1 && l.isk == 0 && l.ise == 1 &&
-                             !at::globalContext().deterministicAlgorithms();
-  bool det = (at::globalContext().deterministicAlgorithms() || prefer_sorted) && floating && (op == OP_SUM || op == OP_MUL);
-  const bool det_sort = det && op == OP_SUM && !coo && l.B == 1 && l.isk == 0 && l.ise == 1;
-  if (sort_sum || csr_minmax || csr_sum || det_sort)
-    ws = at::empty({(int64_t)pyg_hip_scatter_workspace_size(l.B, l.E, l.N)}, src_c.options().dtype(at::kByte));
-  const int base_flags = (coo ? PYG_HIP_SCATTER_SORTED : 0) | (fresh && op == OP_SUM ? PYG_HIP_SCATTER_FRESH_SUM : 0);
-  int rc = pyg_hip_scatter(op, dt, src_c.data_ptr(), l.index.data_ptr<int64_t>(), l.isb, l.ise, l.isk, out.data_ptr(),
-                           minmax ? arg.data_ptr<int64_t>() : nullptr, init.defined() ? init.data_ptr() : nullptr, l.B, l.E,
-                           l.K, l.N, base_flags | (det ? PYG_HIP_SCATTER_DETERMINISTIC : 0),
-                           ws.defined() ? ws.data_ptr() : nullptr, ws.defined() ? (size_t)ws.numel() : 0, stream);
-  if (rc == PYG_HIP_ERR_UNSUPPORTED && det) {
-    if (!prefer_sorted) at::globalContext().alertNotDeterministic(
+  // depend on the order the adds land in); the library ignores the bit for integers and min / max.  Where it has no
+  // atomic-free kernel, torch's own convention applies: alertNotDeterministic raises, or warns under warn_only and the atomic
+  // kernel runs.  (tl_prefer_sorted_sum: scatter_mean's bucket sizes -- see ScatterMean -- ask the same without the alert.)
+  const bool det_mode = at::globalContext().deterministicAlgorithms();
+  int flags = (coo ? PYG_HIP_SCATTER_SORTED : 0) | (fresh && op == OP_SUM ? PYG_HIP_SCATTER_FRESH_SUM : 0) |
+              (det_mode || (tl_prefer_sorted_sum && op == OP_SUM) ? PYG_HIP_SCATTER_DETERMINISTIC : 0);
+  int r = route(flags);
+  if (r == PYG_HIP_SCATTER_ROUTE_UNSUPPORTED) {
+    if (det_mode) at::globalContext().alertNotDeterministic(
         op == OP_MUL ? "pyg::scatter_mul on floating-point HIP tensors"
                      : "pyg::scatter_sum / scatter_mean on HIP tensors with an element-wise (or batched unsorted) index");
-    rc = pyg_hip_scatter(op, dt, src_c.data_ptr(), l.index.data_ptr<int64_t>(), l.isb, l.ise, l.isk, out.data_ptr(),
-                         minmax ? arg.data_ptr<int64_t>() : nullptr, init.defined() ? init.data_ptr() : nullptr, l.B, l.E,
-                         l.K, l.N, base_flags, ws.defined() ? ws.data_ptr() : nullptr,
-                         ws.defined() ? (size_t)ws.numel() : 0, stream);
+    flags &= ~PYG_HIP_SCATTER_DETERMINISTIC;
+    r = route(flags);
   }
-  check_status(rc);
+  Tensor ws;
+  if (r == PYG_HIP_SCATTER_ROUTE_CSR_ROWS || r == PYG_HIP_SCATTER_ROUTE_SORT_ROWS)
+    ws = at::empty({(int64_t)ws_bytes}, src_c.options().dtype(at::kByte));
+  check_status(pyg_hip_scatter(op, dt, src_c.data_ptr(), l.index.data_ptr<int64_t>(), l.isb, l.ise, l.isk, out.data_ptr(),
+                               minmax ? arg.data_ptr<int64_t>() : nullptr, init.defined() ? init.data_ptr() : nullptr, l.B, l.E,
+                               l.K, l.N, flags, ws.defined() ? ws.data_ptr() : nullptr, ws.defined() ? ws_bytes : 0, stream));
   return std::make_tuple(out, arg);
 }
 

@@ -471,13 +471,29 @@ inline unsigned grid_for(int64_t n, int threads = 256) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// workspace of the sort-based scatter: sorted keys + permutation + index_sort's own workspace
-inline size_t scatter_sort_ws_bytes(int64_t E) {
-  return 2 * align_up(sizeof(int64_t) * (size_t)(E > 0 ? E : 1), 256) + index_sort_ws_bytes_i64(E);
-}
-// ... followed by the CSR pointer of the (sorted) index: B * (N + 1) offsets
-inline size_t scatter_indptr_bytes(int64_t B, int64_t N) {
+// ---- the caller's workspace ----------------------------------------------------------------------------------
+// CSR pointer of a sorted index: B * (N + 1) offsets
+inline size_t indptr_bytes(int64_t B, int64_t N) {
   return align_up(sizeof(int64_t) * (size_t)(B > 0 ? B : 1) * (size_t)(N + 1), 256);
+}
+// The one layout, pyg_hip_scatter_workspace_size(B, E, N):  keys | perm | index_sort's scratch | indptr.  The sort-based
+// route (B == 1) uses all four; a sorted index needs `indptr_bytes` only and keeps its offsets in FRONT.
+struct Workspace {
+  int64_t *keys, *perm, *indptr;
+  void* sort_ws;
+  size_t keys_bytes, sort_ws_bytes, bytes;
+};
+Workspace carve(void* ws, int64_t B, int64_t E, int64_t N) {
+  const uintptr_t p = reinterpret_cast<uintptr_t>(ws);  // (may be null: size query)
+  Workspace w;
+  w.keys_bytes = align_up(sizeof(int64_t) * (size_t)(E > 0 ? E : 1), 256);
+  w.sort_ws_bytes = index_sort_ws_bytes_i64(E);
+  w.keys = reinterpret_cast<int64_t*>(p);
+  w.perm = reinterpret_cast<int64_t*>(p + w.keys_bytes);
+  w.sort_ws = reinterpret_cast<void*>(p + 2 * w.keys_bytes);
+  w.indptr = reinterpret_cast<int64_t*>(p + 2 * w.keys_bytes + w.sort_ws_bytes);
+  w.bytes = 2 * w.keys_bytes + w.sort_ws_bytes + indptr_bytes(B, N);
+  return w;
 }
 
 // indptr[b, r] = first position e of row b with index[b, e] >= r (index ascending along e)
@@ -495,190 +511,191 @@ __global__ void coo_indptr_kernel(const int64_t* __restrict__ index, int64_t isb
   indptr[t] = lo;
 }
 
-template <typename T>
-constexpr int dtype_of();
-template <> constexpr int dtype_of<float>() { return PYG_F32; }
-template <> constexpr int dtype_of<double>() { return PYG_F64; }
-template <> constexpr int dtype_of<f16_t>() { return PYG_F16; }
-template <> constexpr int dtype_of<bf16_t>() { return PYG_BF16; }
-template <> constexpr int dtype_of<int8_t>() { return PYG_I8; }
-template <> constexpr int dtype_of<uint8_t>() { return PYG_U8; }
-template <> constexpr int dtype_of<int16_t>() { return PYG_I16; }
-template <> constexpr int dtype_of<int32_t>() { return PYG_I32; }
-template <> constexpr int dtype_of<int64_t>() { return PYG_I64; }
+// ---- the route: which kernel serves a call (the table of pyg_hip_scatter in pyg_hip.h) ------------------------------------
+enum class Route {
+  kNone = PYG_HIP_SCATTER_ROUTE_NONE,                // nothing to do
+  kCsrRows = PYG_HIP_SCATTER_ROUTE_CSR_ROWS,         // sum, min, max: sorted index -> CSR rows
+  kSortRows = PYG_HIP_SCATTER_ROUTE_SORT_ROWS,       // sum, min, max: index sort -> CSR rows through the permutation
+  kVecSorted = PYG_HIP_SCATTER_ROUTE_VEC_SORTED,     // atomic sum: 16-byte slices, runs of 32 sorted positions
+  kVecUnsorted = PYG_HIP_SCATTER_ROUTE_VEC_UNSORTED, // atomic sum: 16-byte slices, 8 positions
+  kPair = PYG_HIP_SCATTER_ROUTE_PAIR,                // atomic sum: packed 16-bit pairs
+  kElem = PYG_HIP_SCATTER_ROUTE_ELEM,                // atomic sum, and mul: one element per thread
+  kAtomicMinMax = PYG_HIP_SCATTER_ROUTE_ATOMIC,      // min, max: value pass + arg pass + reset of the empty buckets
+  kUnsupported = PYG_HIP_SCATTER_ROUTE_UNSUPPORTED,  // PYG_HIP_SCATTER_DETERMINISTIC, and no atomic-free kernel
+};
+inline bool rows_route(Route r) { return r == Route::kCsrRows || r == Route::kSortRows; }
+inline const char* route_name(Route r) {
+  static const char* const names[] = {"none", "csr_rows", "sort_rows", "vec_sorted", "vec_unsorted", "pair", "elem", "atomic", "unsupported"};
+  return names[(int)r];
+}
+// pyg_hip_scatter_last_route(): the route of the last pyg_hip_scatter on this thread
+thread_local Route g_last_route = Route::kNone;
 
+struct Flags {  // the PYG_HIP_SCATTER_* bits of a call, decoded
+  bool sorted, fresh_sum, cas, deterministic;
+  explicit Flags(int f)
+      : sorted(f & PYG_HIP_SCATTER_SORTED), fresh_sum(f & PYG_HIP_SCATTER_FRESH_SUM), cas(f & PYG_HIP_SCATTER_CAS),
+        deterministic(f & PYG_HIP_SCATTER_DETERMINISTIC) {}
+};
+
+// The thresholds of the choice.
+// One large unsorted index vector, for sums with rows of >= 64 bytes: sort the E indices once (3-4 radix passes over 16 E
+// bytes), buckets become CSR rows reduced through the permutation in SOURCE order (the stable sort keeps it): no atomics,
+// deterministic, every output row written once.
+constexpr int64_t kSortMinEntries = 1 << 15;
+constexpr int64_t kSortMinRowBytes = 64;
+// Unsorted NARROW rows -- up to four 16-byte slices -- stay away from the slice kernel: a thread of it owns 8 consecutive
+// edges of one slice, so with few slices per row its lanes are 128+ bytes apart on every load, and every lane's four atomics
+// hit a line of their own.  One element / one packed pair per thread puts neighbouring lanes on neighbouring words of the
+// same row: K = 4 floats, 20 M edges: 3.9 ms there, 0.96 here (= torch.index_add_); bf16 K = 16: 3.9 -> 1.0.
+constexpr int64_t kNarrowSlices = 4;
+// The slice kernel needs 16-byte aligned `src` and `out`, the pair kernel whole 32-bit words (K even, bases 4-byte aligned).
+constexpr unsigned kSliceAlignMask = 15, kPairAlignMask = 3;
+
+struct RowsNeed {  // what each rows route needs of the caller's workspace (from the one layout above)
+  size_t csr_rows, sort_rows;
+};
+inline RowsNeed rows_need(const Shape& s) { return RowsNeed{indptr_bytes(s.B, s.N), carve(nullptr, 1, s.E, s.N).bytes}; }
+
+// The route of a call with a valid `op` and `dtype`.  `workspace_bytes`: what the caller offers (0: nothing); `misalign`:
+// the low four bits of src | out, which only decide among the slice, pair and element kernels.  Pure: no HIP call, no global.
+Route choose_scatter_route(int op, int dtype, const Shape& s, const Flags& f, size_t workspace_bytes, const RowsNeed& need,
+                           unsigned misalign) {
+  if (s.B * s.E * s.K == 0) return Route::kNone;
+  const int64_t size = (int64_t)dtype_size(dtype);
+  const bool half = dtype == PYG_BF16 || dtype == PYG_F16;
+  const bool float_t = dtype == PYG_F32 || half;  // what the slice kernel and the automatic sort-based sum take
+  const bool floating = float_t || dtype == PYG_F64;
+  const bool minmax = op == OP_MIN || op == OP_MAX;
+  // Atomic-free: with an index broadcast along k and the caller's workspace, buckets are CSR rows -- as the index stands if it
+  // ascends along e (the COO contract), or after sorting one index vector -- walked in source order (min / max: with the
+  // reference's strict compare: values and first-match arg exact, no CAS loops, no second pass).
+  if ((op == OP_SUM || minmax) && s.isk == 0) {
+    if (f.sorted && workspace_bytes >= need.csr_rows) return Route::kCsrRows;
+    const bool large = s.E >= kSortMinEntries && (minmax || (float_t && s.K * size >= kSortMinRowBytes));
+    // PYG_HIP_SCATTER_DETERMINISTIC: the same route for a sum of ANY size, row width and floating type (float64 included)
+    const bool forced = op == OP_SUM && f.deterministic && floating;
+    if (!f.sorted && s.B == 1 && s.ise == 1 && (large || forced) && workspace_bytes >= need.sort_rows) return Route::kSortRows;
+  }
+  if (f.deterministic && floating && (op == OP_SUM || op == OP_MUL)) return Route::kUnsupported;
+  if (minmax) return Route::kAtomicMinMax;
+  if (op == OP_MUL) return Route::kElem;
+  const int64_t slices = s.K / (16 / size);  // 16-byte slices of a row of whole slices
+  if (float_t && s.isk == 0 && s.K % (16 / size) == 0 && (misalign & kSliceAlignMask) == 0 && (f.sorted || slices > kNarrowSlices))
+    return f.sorted ? Route::kVecSorted : Route::kVecUnsorted;
+  if (half && s.isk == 0 && s.K % 2 == 0 && !f.sorted && (misalign & kPairAlignMask) == 0) return Route::kPair;
+  return Route::kElem;
+}
+
+// ---- the rows routes: CSR rows for csr.hip -------------------------------------------------------------------------------
+struct Rows {  // `perm`: source row of sorted position e, or null; `scratch`: for hub rows
+  const int64_t *indptr, *perm;
+  void* scratch;
+  size_t scratch_bytes;
+};
+
+int launch_indptr(const int64_t* index, int64_t isb, int64_t ise, const Shape& s, int64_t* indptr, hipStream_t stream) {
+  const int64_t n = s.B * (s.N + 1);
+  hipLaunchKernelGGL(coo_indptr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, index, isb, ise, s.B, s.E,
+                     s.N, indptr);
+  PYG_HIP_CHECK(hipGetLastError());
+  return PYG_HIP_OK;
+}
+
+// COO contract (index ascending along e): buckets are CSR rows -- reduced in source order in opmath, seeded from `out`, no
+// atomics (the run accumulation of segment_coo_kernel.cpp:104-166, bit for bit)
+int rows_of_sorted_index(const int64_t* index, const Shape& s, void* ws, size_t ws_bytes, hipStream_t stream, Rows* rows) {
+  const size_t ip_bytes = indptr_bytes(s.B, s.N);
+  // (what the workspace holds behind the offsets is scratch for hub rows)
+  *rows = Rows{static_cast<int64_t*>(ws), nullptr, static_cast<char*>(ws) + ip_bytes, ws_bytes - ip_bytes};
+  return launch_indptr(index, s.isb, s.ise, s, static_cast<int64_t*>(ws), stream);
+}
+
+// One unsorted index vector (B == 1): stable sort, then the offsets of the sorted keys; rows are read through the permutation
+int rows_by_index_sort(const int64_t* index, const Shape& s, void* ws, hipStream_t stream, Rows* rows) {
+  const Workspace w = carve(ws, 1, s.E, s.N);
+  // (the sorted keys are dead once the offsets exist: scratch for hub rows)
+  *rows = Rows{w.indptr, w.perm, w.keys, w.keys_bytes};
+  const int rc = index_sort_i64(index, s.E, s.N > 0 ? s.N - 1 : 0, w.keys, w.perm, w.sort_ws, w.sort_ws_bytes, stream);
+  return rc != PYG_HIP_OK ? rc : launch_indptr(w.keys, 0, 1, s, w.indptr, stream);
+}
+
+// ---- the atomic routes ---------------------------------------------------------------------------------------------------
+template <typename... P, typename... A>
+int launch(void (*kernel)(P...), int64_t threads, hipStream_t stream, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid_for(threads)), dim3(256), 0, stream, args...);
+  PYG_HIP_CHECK(hipGetLastError());
+  return PYG_HIP_OK;
+}
+
+// `cas`: the compare-and-swap flavour of the floating adds (PYG_HIP_SCATTER_CAS or the process default)
 template <typename T>
-int run_scatter(int op, const void* src_, const int64_t* index, void* out_, int64_t* arg, const void* init_,
-                const Shape& s, int sorted, void* ws, size_t ws_bytes, hipStream_t stream) {
+int run_atomic(Route route, int op, bool cas, const void* src_, const int64_t* index, void* out_, int64_t* arg,
+               const void* init_, const Shape& s, hipStream_t stream) {
   const T* src = static_cast<const T*>(src_);
   T* out = static_cast<T*>(out_);
   const T* init = static_cast<const T*>(init_);
+  constexpr bool half = std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value;
   const int64_t total = s.B * s.E * s.K;
   const int64_t outn = s.B * s.N * s.K;
-  // PYG_HIP_SCATTER_FRESH_SUM: `out` of a sum is uninitialised.  The sorted (CSR-row) path writes every slot and never
-  // reads it; every other path accumulates into zeros, cleared here.
-  const bool fresh_sum = op == OP_SUM && (sorted & PYG_HIP_SCATTER_FRESH_SUM) != 0;
-  const bool cas = (sorted & PYG_HIP_SCATTER_CAS) != 0 || float_atomic_mode() == 1;
-  const bool det = (sorted & PYG_HIP_SCATTER_DETERMINISTIC) != 0;
-  sorted &= PYG_HIP_SCATTER_SORTED;
-  const bool csr_rows = op == OP_SUM && sorted && s.isk == 0 && ws && ws_bytes >= scatter_indptr_bytes(s.B, s.N) && total > 0;
-  // one large unsorted index vector, rows of >= 64 bytes: sort the E indices once (3-4 radix passes over 16 E bytes),
-  // buckets become CSR rows summed through the permutation in SOURCE order (the stable sort keeps it): no atomics,
-  // deterministic, every output row written once
-  const bool float_t = std::is_same<T, float>::value || std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value;
-  // PYG_HIP_SCATTER_DETERMINISTIC: the same path for ANY size, row width and floating type (float64 included)
-  const bool floating = float_t || std::is_same<T, double>::value;
-  const bool sort_rows = op == OP_SUM && !sorted && s.isk == 0 && s.B == 1 && s.ise == 1 && ws &&
-                         ws_bytes >= scatter_sort_ws_bytes(s.E) + scatter_indptr_bytes(1, s.N) &&
-                         ((float_t && s.E >= (1 << 15) && s.K * (int64_t)sizeof(T) >= 64) || (det && floating && s.E > 0));
-  if (det && floating && total > 0 && ((op == OP_SUM && !csr_rows && !sort_rows) || op == OP_MUL))
-    return fail(PYG_HIP_ERR_UNSUPPORTED,
-                "scatter: no atomic-free kernel for this reduction / index layout (PYG_HIP_SCATTER_DETERMINISTIC: floating sums "
-                "need an index broadcast along k -- sorted, or one unsorted vector -- and the caller's workspace)");
-  if (fresh_sum && !csr_rows && !sort_rows && outn > 0) PYG_HIP_CHECK(hipMemsetAsync(out, 0, sizeof(T) * (size_t)outn, stream));
-  if (total == 0) return PYG_HIP_OK;
-  if (op == OP_SUM && !csr_rows && !sort_rows && (std::is_floating_point<T>::value || float_t))
-    note_accumulate("pyg_hip_scatter (sum, atomic kernels)", out, sizeof(T) * (size_t)outn,
-                    fresh_sum ? "this call (hipMemsetAsync on the call's stream)" : "the caller (`out=` accumulation)", stream, cas ? 1 : 0);
-  const unsigned grid = grid_for(total);
-  if (csr_rows) {
-    // COO contract (index ascending along e): buckets are CSR rows -- summed in source order in opmath,
-    // seeded from `out`, no atomics (the run accumulation of segment_coo_kernel.cpp:104-166, bit for bit)
-    int64_t* indptr = reinterpret_cast<int64_t*>(ws);
-    const int64_t n = s.B * (s.N + 1);
-    hipLaunchKernelGGL(coo_indptr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, index, s.isb, s.ise,
-                       s.B, s.E, s.N, indptr);
-    PYG_HIP_CHECK(hipGetLastError());
-    // (what the workspace holds behind the offsets is scratch for hub rows)
-    const size_t ip_bytes = scatter_indptr_bytes(s.B, s.N);
-    return segment_csr_sum(dtype_of<T>(), src, indptr, s.N + 1, nullptr, out, s.B, s.N, s.E, s.K, fresh_sum ? 1 : 0, stream,
-                           static_cast<char*>(ws) + ip_bytes, ws_bytes - ip_bytes);
+  const int64_t* no_perm = nullptr;
+  if constexpr (std::is_same<T, float>::value || half) {
+    const int64_t kv = s.K / Vec<T>::N;
+    if (route == Route::kVecSorted)
+      return launch(cas ? scatter_sum_vec_kernel<T, true, true> : scatter_sum_vec_kernel<T, true>, s.B * ((s.E + 31) / 32) * kv,
+                    stream, src, index, no_perm, out, s);
+    if (route == Route::kVecUnsorted)
+      return launch(cas ? scatter_sum_vec_kernel<T, false, true> : scatter_sum_vec_kernel<T, false>, s.B * ((s.E + 7) / 8) * kv,
+                    stream, src, index, no_perm, out, s);
   }
-  if (sort_rows) {
-    char* w = static_cast<char*>(ws);
-    const size_t sort_bytes = scatter_sort_ws_bytes(s.E);
-    int64_t* keys = reinterpret_cast<int64_t*>(w);
-    int64_t* perm = reinterpret_cast<int64_t*>(w + align_up(sizeof(int64_t) * (size_t)s.E, 256));
-    void* sws = w + 2 * align_up(sizeof(int64_t) * (size_t)s.E, 256);
-    int64_t* indptr = reinterpret_cast<int64_t*>(w + sort_bytes);
-    int rc = index_sort_i64(index, s.E, s.N > 0 ? s.N - 1 : 0, keys, perm, sws,
-                            sort_bytes - 2 * align_up(sizeof(int64_t) * (size_t)s.E, 256), stream);
-    if (rc != PYG_HIP_OK) return rc;
-    hipLaunchKernelGGL(coo_indptr_kernel, dim3((unsigned)((s.N + 1 + 255) / 256)), dim3(256), 0, stream,
-                       (const int64_t*)keys, (int64_t)0, (int64_t)1, (int64_t)1, s.E, s.N, indptr);
-    PYG_HIP_CHECK(hipGetLastError());
-    // (the sorted keys are dead once the offsets exist: scratch for hub rows)
-    return segment_csr_sum(dtype_of<T>(), src, indptr, s.N + 1, perm, out, 1, s.N, s.E, s.K, fresh_sum ? 1 : 0, stream, keys,
-                           align_up(sizeof(int64_t) * (size_t)s.E, 256));
+  if constexpr (half) {
+    if (route == Route::kPair)
+      return launch(cas ? scatter_sum_pair_kernel<T, true> : scatter_sum_pair_kernel<T, false>, s.B * s.E * (s.K / 2), stream,
+                    src, index, out, s);
   }
-  if (op == OP_SUM) {
-    if constexpr (std::is_same<T, float>::value || std::is_same<T, bf16_t>::value ||
-                  std::is_same<T, f16_t>::value) {
-      // (unsorted NARROW rows -- up to four 16-byte slices -- do not come here: a thread of the kernel below owns 8 consecutive
-      // edges of one slice, so with few slices per row its lanes are 128+ bytes apart on every load, and every lane's four
-      // atomics hit a line of their own.  One element / one packed pair per thread -- the kernels further down -- puts
-      // neighbouring lanes on neighbouring words of the same row: K = 4 floats, 20 M edges: 3.9 ms here, 0.96 there (=
-      // torch.index_add_); bf16 K = 16: 3.9 -> 1.0.)
-      const bool narrow = !sorted && s.K / Vec<T>::N <= 4;
-      if (s.isk == 0 && s.K % Vec<T>::N == 0 && aligned16(src) && aligned16(out) && !narrow) {
-        if (sorted) {
-          const int64_t threads = s.B * ((s.E + 31) / 32) * (s.K / Vec<T>::N);
-          if (cas)
-            hipLaunchKernelGGL((scatter_sum_vec_kernel<T, true, true>), dim3(grid_for(threads)), dim3(256), 0, stream, src,
-                               index, (const int64_t*)nullptr, out, s);
-          else
-            hipLaunchKernelGGL((scatter_sum_vec_kernel<T, true>), dim3(grid_for(threads)), dim3(256), 0, stream,
-                               src, index, (const int64_t*)nullptr, out, s);
-          PYG_HIP_CHECK(hipGetLastError());
-          return PYG_HIP_OK;
-        }
-        const int64_t threads = s.B * ((s.E + 7) / 8) * (s.K / Vec<T>::N);
-        if (cas)
-          hipLaunchKernelGGL((scatter_sum_vec_kernel<T, false, true>), dim3(grid_for(threads)), dim3(256), 0, stream, src,
-                             index, (const int64_t*)nullptr, out, s);
-        else
-          hipLaunchKernelGGL((scatter_sum_vec_kernel<T, false>), dim3(grid_for(threads)), dim3(256), 0, stream,
-                             src, index, (const int64_t*)nullptr, out, s);
-        PYG_HIP_CHECK(hipGetLastError());
-        return PYG_HIP_OK;
-      }
-    }
-    if constexpr (std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value) {
-      // 16-bit rows of an even number of elements: packed pairs (4-byte aligned: K even, bases 4-byte aligned)
-      if (s.isk == 0 && s.K % 2 == 0 && !sorted && (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0) {
-        const int64_t threads = s.B * s.E * (s.K / 2);
-        if (cas)
-          hipLaunchKernelGGL((scatter_sum_pair_kernel<T, true>), dim3(grid_for(threads)), dim3(256), 0, stream, src, index, out, s);
-        else
-          hipLaunchKernelGGL((scatter_sum_pair_kernel<T, false>), dim3(grid_for(threads)), dim3(256), 0, stream, src, index, out, s);
-        PYG_HIP_CHECK(hipGetLastError());
-        return PYG_HIP_OK;
-      }
-    }
-    if constexpr (std::is_same<T, float>::value || std::is_same<T, double>::value) {
-      if (cas) {
-        hipLaunchKernelGGL((scatter_elem_kernel<T, OP_SUM, true>), dim3(grid), dim3(256), 0, stream, src, index, out, s);
-        PYG_HIP_CHECK(hipGetLastError());
-        return PYG_HIP_OK;
-      }
-    }
-    hipLaunchKernelGGL((scatter_elem_kernel<T, OP_SUM>), dim3(grid), dim3(256), 0, stream, src, index, out, s);
-  } else if (op == OP_MUL) {
-    hipLaunchKernelGGL((scatter_elem_kernel<T, OP_MUL>), dim3(grid), dim3(256), 0, stream, src, index, out, s);
-  } else if (op == OP_MIN || op == OP_MAX) {
-    PYG_HIP_REQUIRE(arg != nullptr, "scatter_min/max: 'arg_out' is NULL");
-    // Atomic-free path: with the index ascending along e (the COO contract), or after sorting one
-    // index vector, buckets are CSR rows -- one thread per (bucket, 16-byte slice) walks its row in
-    // source order with the reference's strict compare (values and first-match arg exact, no CAS
-    // loops, no second pass).  Needs an index broadcast along k and the caller's workspace.
-    if (s.isk == 0 && ws) {
-      char* w = static_cast<char*>(ws);
-      const size_t ip_bytes = scatter_indptr_bytes(s.B, s.N);
-      if (sorted && ws_bytes >= ip_bytes) {
-        int64_t* indptr = reinterpret_cast<int64_t*>(w);
-        const int64_t n = s.B * (s.N + 1);
-        hipLaunchKernelGGL(coo_indptr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, index, s.isb,
-                           s.ise, s.B, s.E, s.N, indptr);
-        PYG_HIP_CHECK(hipGetLastError());
-        return segment_csr_minmax(op == OP_MIN, dtype_of<T>(), src, indptr, s.N + 1, nullptr, out, arg, init ? 0 : 1,
-                                  s.B, s.N, s.E, s.K, stream, w + ip_bytes, ws_bytes - ip_bytes);
-      }
-      const size_t sort_bytes = scatter_sort_ws_bytes(s.E);
-      if (!sorted && s.B == 1 && s.ise == 1 && s.E >= (1 << 15) && ws_bytes >= sort_bytes + scatter_indptr_bytes(1, s.N)) {
-        int64_t* keys = reinterpret_cast<int64_t*>(w);
-        int64_t* perm = reinterpret_cast<int64_t*>(w + align_up(sizeof(int64_t) * (size_t)s.E, 256));
-        void* sws = w + 2 * align_up(sizeof(int64_t) * (size_t)s.E, 256);
-        int64_t* indptr = reinterpret_cast<int64_t*>(w + sort_bytes);
-        int rc = index_sort_i64(index, s.E, s.N > 0 ? s.N - 1 : 0, keys, perm, sws,
-                                sort_bytes - 2 * align_up(sizeof(int64_t) * (size_t)s.E, 256), stream);
-        if (rc != PYG_HIP_OK) return rc;
-        hipLaunchKernelGGL(coo_indptr_kernel, dim3((unsigned)((s.N + 1 + 255) / 256)), dim3(256), 0, stream,
-                           (const int64_t*)keys, (int64_t)0, (int64_t)1, (int64_t)1, s.E, s.N, indptr);
-        PYG_HIP_CHECK(hipGetLastError());
-        return segment_csr_minmax(op == OP_MIN, dtype_of<T>(), src, indptr, s.N + 1, perm, out, arg, init ? 0 : 1, 1,
-                                  s.N, s.E, s.K, stream, keys, align_up(sizeof(int64_t) * (size_t)s.E, 256));
-      }
-    }
-    hipLaunchKernelGGL(fill_i64_kernel, dim3((unsigned)((outn + 255) / 256)), dim3(256), 0, stream, arg, outn,
-                       s.E);
-    if (op == OP_MIN) {
-      hipLaunchKernelGGL((scatter_elem_kernel<T, OP_MIN>), dim3(grid), dim3(256), 0, stream, src, index, out, s);
-      hipLaunchKernelGGL((scatter_arg_kernel<T, true>), dim3(grid), dim3(256), 0, stream, src, index, out, init,
-                         arg, s);
-    } else {
-      hipLaunchKernelGGL((scatter_elem_kernel<T, OP_MAX>), dim3(grid), dim3(256), 0, stream, src, index, out, s);
-      hipLaunchKernelGGL((scatter_arg_kernel<T, false>), dim3(grid), dim3(256), 0, stream, src, index, out, init,
-                         arg, s);
-    }
-    // (integers: equal values are equal bits, only the reset of a fresh output's empty buckets is left to do)
-    if (!init || std::is_floating_point<T>::value || std::is_same<T, bf16_t>::value || std::is_same<T, f16_t>::value)
-      hipLaunchKernelGGL((minmax_finish_kernel<T>), dim3((unsigned)((outn + 255) / 256)), dim3(256), 0, stream, src, out,
-                         arg, init ? 0 : 1, s);
-  } else {
-    return fail(PYG_HIP_ERR_INVALID, "scatter: unknown reduce op %d", op);
+  if (op == OP_MUL) return launch(scatter_elem_kernel<T, OP_MUL>, total, stream, src, index, out, s);
+  if (op == OP_SUM) {  // (of the element adds, only float and double have a CAS form of their own)
+    constexpr bool kHasCas = std::is_same<T, float>::value || std::is_same<T, double>::value;
+    return launch(cas ? scatter_elem_kernel<T, OP_SUM, kHasCas> : scatter_elem_kernel<T, OP_SUM>, total, stream, src, index,
+                  out, s);
   }
+  const unsigned grid = grid_for(total), ogrid = (unsigned)((outn + 255) / 256);
+  hipLaunchKernelGGL(fill_i64_kernel, dim3(ogrid), dim3(256), 0, stream, arg, outn, s.E);
+  const auto value_pass = op == OP_MIN ? scatter_elem_kernel<T, OP_MIN> : scatter_elem_kernel<T, OP_MAX>;
+  const auto arg_pass = op == OP_MIN ? scatter_arg_kernel<T, true> : scatter_arg_kernel<T, false>;
+  hipLaunchKernelGGL(value_pass, dim3(grid), dim3(256), 0, stream, src, index, out, s);
+  hipLaunchKernelGGL(arg_pass, dim3(grid), dim3(256), 0, stream, src, index, out, init, arg, s);
+  // (integers: equal values are equal bits, only the reset of a fresh output's empty buckets is left to do)
+  if (!init || std::is_floating_point<T>::value || half)
+    hipLaunchKernelGGL((minmax_finish_kernel<T>), dim3(ogrid), dim3(256), 0, stream, src, out, arg, init ? 0 : 1, s);
   PYG_HIP_CHECK(hipGetLastError());
   return PYG_HIP_OK;
+}
+
+// Runs a kernel route (not kNone, not kUnsupported).
+int run_scatter(Route route, int op, int dtype, const void* src, const int64_t* index, void* out, int64_t* arg,
+                const void* init, const Shape& s, const Flags& f, void* ws, size_t ws_bytes, hipStream_t stream) {
+  const size_t out_bytes = dtype_size(dtype) * (size_t)(s.B * s.N * s.K);
+  const bool fresh_sum = op == OP_SUM && f.fresh_sum;
+  if (rows_route(route)) {
+    Rows r;
+    const int rc = route == Route::kCsrRows ? rows_of_sorted_index(index, s, ws, ws_bytes, stream, &r)
+                                            : rows_by_index_sort(index, s, ws, stream, &r);
+    if (rc != PYG_HIP_OK) return rc;
+    if (op == OP_SUM)
+      return segment_csr_sum(dtype, src, r.indptr, s.N + 1, r.perm, out, s.B, s.N, s.E, s.K, fresh_sum ? 1 : 0, stream,
+                             r.scratch, r.scratch_bytes);
+    return segment_csr_minmax(op == OP_MIN, dtype, src, r.indptr, s.N + 1, r.perm, out, arg, init ? 0 : 1, s.B, s.N, s.E, s.K,
+                              stream, r.scratch, r.scratch_bytes);
+  }
+  // PYG_HIP_SCATTER_FRESH_SUM: `out` of a sum is uninitialised.  The rows routes write every slot and never read it; the
+  // atomic routes accumulate into zeros, cleared here.
+  if (fresh_sum && out_bytes > 0) PYG_HIP_CHECK(hipMemsetAsync(out, 0, out_bytes, stream));
+  const bool cas = f.cas || float_atomic_mode() == 1;
+  if (op == OP_SUM && (dtype == PYG_F32 || dtype == PYG_F64 || dtype == PYG_BF16 || dtype == PYG_F16))
+    note_accumulate("pyg_hip_scatter (sum, atomic kernels)", out, out_bytes,
+                    fresh_sum ? "this call (hipMemsetAsync on the call's stream)" : "the caller (`out=` accumulation)", stream, cas ? 1 : 0);
+  PYG_DISPATCH_ALL(dtype, (run_atomic<scalar_t>(route, op, cas, src, index, out, arg, init, s, stream)));
 }
 
 template <typename T>
@@ -721,14 +738,25 @@ using namespace pyg_hip;
 extern "C" {
 
 size_t pyg_hip_scatter_workspace_size(int64_t B, int64_t E, int64_t N) {
-  return scatter_sort_ws_bytes(E < 0 ? 0 : E) + scatter_indptr_bytes(B < 1 ? 1 : B, N < 0 ? 0 : N);
+  return carve(nullptr, B < 1 ? 1 : B, E < 0 ? 0 : E, N < 0 ? 0 : N).bytes;
 }
+
+int pyg_hip_scatter_route(int op, int dtype, int64_t index_stride_b, int64_t index_stride_e, int64_t index_stride_k, int64_t B,
+                          int64_t E, int64_t K, int64_t N, int flags, size_t workspace_bytes, unsigned misalign) {
+  if (op < OP_SUM || op > OP_MAX || dtype_size(dtype) == 0 || B < 0 || E < 0 || K < 0 || N < 0)
+    return PYG_HIP_SCATTER_ROUTE_UNSUPPORTED;
+  const Shape s{B, E, K, N, index_stride_b, index_stride_e, index_stride_k};
+  return (int)choose_scatter_route(op, dtype, s, Flags(flags), workspace_bytes, rows_need(s), misalign);
+}
+
+const char* pyg_hip_scatter_last_route(void) { return route_name(g_last_route); }
 
 int pyg_hip_scatter(int op, int dtype, const void* src, const int64_t* index, int64_t index_stride_b,
                     int64_t index_stride_e, int64_t index_stride_k, void* out, int64_t* arg_out,
                     const void* out_init, int64_t B, int64_t E, int64_t K, int64_t N, int index_sorted,
                     void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
+  g_last_route = Route::kNone;
   PYG_HIP_REQUIRE(B >= 0 && E >= 0 && K >= 0 && N >= 0, "scatter: negative size");
   if (B * E * K == 0) {
     if (op == OP_SUM && (index_sorted & PYG_HIP_SCATTER_FRESH_SUM) && out && B * N * K > 0)
@@ -741,9 +769,20 @@ int pyg_hip_scatter(int op, int dtype, const void* src, const int64_t* index, in
     return PYG_HIP_OK;
   }
   PYG_HIP_REQUIRE(src && index && out, "scatter: NULL tensor");
-  Shape s{B, E, K, N, index_stride_b, index_stride_e, index_stride_k};
-  PYG_DISPATCH_ALL(dtype, (run_scatter<scalar_t>(op, src, index, out, arg_out, out_init, s, index_sorted, workspace,
-                                                 workspace_bytes, stream)));
+  PYG_HIP_REQUIRE(dtype_size(dtype) != 0, "unknown dtype %d", dtype);
+  PYG_HIP_REQUIRE(op >= OP_SUM && op <= OP_MAX, "scatter: unknown reduce op %d", op);
+  PYG_HIP_REQUIRE((op != OP_MIN && op != OP_MAX) || arg_out != nullptr, "scatter_min/max: 'arg_out' is NULL");
+  const Shape s{B, E, K, N, index_stride_b, index_stride_e, index_stride_k};
+  const Flags f(index_sorted);
+  const size_t offered = workspace ? workspace_bytes : 0;
+  const unsigned misalign = (unsigned)((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out)) & 15);
+  const Route route = choose_scatter_route(op, dtype, s, f, offered, rows_need(s), misalign);
+  g_last_route = route;
+  if (route == Route::kUnsupported)
+    return fail(PYG_HIP_ERR_UNSUPPORTED,
+                "scatter: no atomic-free kernel for this reduction / index layout (PYG_HIP_SCATTER_DETERMINISTIC: floating sums "
+                "need an index broadcast along k -- sorted, or one unsorted vector -- and the caller's workspace)");
+  return run_scatter(route, op, dtype, src, index, out, arg_out, out_init, s, f, workspace, offered, stream);
 }
 
 int pyg_hip_fill_reduce_identity(int op, int dtype, void* out, int64_t n, void* stream_) {

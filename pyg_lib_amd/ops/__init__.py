@@ -432,6 +432,15 @@ def matmul_last_variant() -> str:
     return _capi.lib().pyg_hip_matmul_last_variant().decode()
 
 
+def scatter_last_route() -> str:
+    """Name of the route the last ``pyg_hip_scatter`` call made FROM THE CALLING THREAD took -- the last ``scatter_*`` /
+    ``segment_*_coo`` op, for ``scatter_mean`` its count (test/diagnostic hook): ``'csr_rows'`` / ``'sort_rows'`` (atomic-free
+    CSR rows: sorted index / after an index sort), ``'vec_sorted'`` / ``'vec_unsorted'`` / ``'pair'`` / ``'elem'`` (atomic sums;
+    ``'elem'`` also mul), ``'atomic'`` (min / max), ``'none'`` (nothing to do); the rules are the table of ``pyg_hip_scatter``
+    in include/pyg_hip.h."""
+    return _capi.lib().pyg_hip_scatter_last_route().decode()
+
+
 def matmul_dw_counters() -> Tuple[int, int]:
     """(specialised, general): calls served by the shape-specialised / the general-shape weight-gradient kernels since the
     library was loaded (process wide -- the backward pass runs on an autograd thread)."""

@@ -48,6 +48,7 @@ FLOATS = (torch.float32, torch.float64, torch.bfloat16, torch.float16)
 def lib():
     L = c.CDLL(osp.join(ROOT, 'pyg_lib_amd', 'libpyg_hip.so'))
     L.pyg_hip_last_error.restype = c.c_char_p
+    L.pyg_hip_scatter_last_route.restype = c.c_char_p
     for name, res, args in (
             ('pyg_hip_scatter_workspace_size', SZ, [I64, I64, I64]),
             ('pyg_hip_scatter', I32, [I32, I32, P, P, I64, I64, I64, P, P, P, I64, I64, I64, I64, I32, P, SZ, P]),
@@ -626,6 +627,7 @@ def test_scatter_paths(lib, name, dtype, op, flags, with_ws, B, E, K, N, path):
         finally:
             diagnostics.set_float_atomic_mode(before)
         what = f'{name} [{mode}{"+CAS flag" if mode_flags else ""}{" fresh" if fresh_minmax else ""}]'
+        assert lib.pyg_hip_scatter_last_route().decode() == path, what       # ... and the library ran the path of the label
         fresh = bool(flags & FRESH) or fresh_minmax
         if op != MUL:
             assert want_classes(opn, fresh) <= classes_in(want, bf16), (what, classes_in(want, bf16))
