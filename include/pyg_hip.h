@@ -57,6 +57,8 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  13: pyg_hip_knn / _knn_emit, pyg_hip_radius / _radius_emit, pyg_hip_nearest, pyg_hip_spatial_route / _last_route / _tile /
+ *      _workspace_size, pyg_hip_nearest_pending_error (batched point-cloud neighbour search).
  *  12: pyg_hip_scatter_route, pyg_hip_scatter_last_route (which kernel serves a scatter call: asked without running, told after).
  *  11: pyg_hip_fused_scatter_reduce, its _workspace_size and _backward (sum / mean / min / max in one sort and one pass).
  *  10: pyg_hip_sampled_op, pyg_hip_sampled_op_backward (fused gather + binary operator and its per-edge gradients).
@@ -70,7 +72,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 12
+#define PYG_HIP_ABI_VERSION 13
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -850,6 +852,87 @@ PYG_HIP_API int pyg_hip_fused_scatter_reduce_backward(int dtype, const void* gra
                                                       const int64_t* arg_min, const int64_t* arg_max, const int64_t* count,
                                                       int64_t E, int64_t F, int64_t N, const int* ops, int n_ops, void* grad_in,
                                                       void* stream);
+
+/* ---- knn, radius, nearest: batched point-cloud neighbour search -------------------------------------------------
+ *
+ * Replace pyg::knn / pyg::radius / pyg::nearest (schemas ops/{knn,radius,nearest}.cpp; CUDA ops/cuda/{knn,radius,nearest}_kernel.cu).
+ * knn and radius: x [N, D] are the candidates, y [M, D] the queries; nearest: x [N, D] are the queries, y [M, D] the candidates.
+ * Row-major, one floating `dtype` (PYG_F32 / F64 / F16 / BF16) for both, 1 <= D <= 4096.  ptr_x / ptr_y: int64 CSR pointers of
+ * num_examples + 1 entries on the device; NULL means the single example [0, rows] (num_examples must then be 1 for both).
+ * Example b pairs the queries ptr_q[b] .. ptr_q[b + 1] with the candidates ptr_c[b] .. ptr_c[b + 1].
+ *
+ * Distance: squared Euclidean, dist = 0; for d = 0 .. D-1: diff = a[d] - b[d]; dist = dist + diff * diff -- every operation
+ * rounded on its own, NO fused multiply-add, in fp32 (fp64 for PYG_F64; 16-bit inputs are widened exactly).  This is the
+ * arithmetic of the reference's CPU `nearest` loop, so the device and a plain CPU loop agree bit for bit, near-ties included.
+ * A candidate at distance NaN or +Inf is never returned by any of the three.
+ *
+ * knn:     per query i (ascending) the eligible candidates of its example ordered by (distance, index); the first
+ *          min(k, eligible) become columns (i, j) of out [2, E].  1 <= k <= 100 (more: PYG_HIP_ERR_UNSUPPORTED, the
+ *          reference's limit).  PYG_HIP_SPATIAL_COSINE: the distance is 1 - dot / (|x| |y|), norms computed once per point.
+ * radius:  a candidate matches when dist < (compute type)(r * r), the product formed in double; per query the first
+ *          max_num_neighbors matches in ascending candidate index are kept; PYG_HIP_SPATIAL_IGNORE_SAME drops j == i (global
+ *          indices); out [2, E] ordered by (i, j) -- the rule of the reference's CUDA kernel.
+ * nearest: out[i] = the first index of the example's y range at the smallest eligible distance; a query without an eligible
+ *          candidate gets the clamped ptr_y[b] (which can equal M).
+ *
+ * Pointers: every segment bound is clamped into [0, rows] before use, so a bad pointer never causes an access outside the
+ * buffers.  A pointer that decreases, or whose last entry is not the row count, is reported: by knn / radius in the call
+ * (PYG_HIP_ERR_INVALID; they read the pair count back anyway), by nearest -- which never synchronises -- through a pinned
+ * word of the device: the NEXT pyg_hip_nearest call on that device fails with PYG_HIP_ERR_INVALID, and
+ * pyg_hip_nearest_pending_error() returns and clears the word (meaningful once the stream has been synchronised).
+ *
+ * Two calls for knn and radius, because the caller allocates the output: pyg_hip_knn / pyg_hip_radius run the search into the
+ * workspace, wait for `stream` once and return the pair count E in *num_pairs (host); pyg_hip_knn_emit / pyg_hip_radius_emit,
+ * given the SAME arguments and workspace, write out [2, E] (int64) without synchronising.  Everything is queued on `stream`.
+ * Fewer than 2^31 rows in x and in y (PYG_HIP_ERR_UNSUPPORTED otherwise: indices inside the kernels are 32-bit); pair counts
+ * and output offsets are 64-bit.  workspace: pyg_hip_spatial_workspace_size(...) bytes for the same arguments and flags,
+ * 16-byte aligned; less is PYG_HIP_ERR_WORKSPACE.
+ *
+ * Routes.  pyg_hip_spatial_route(op, dtype, M, N, B, D, k) -- M queries, N candidates, B examples -- answers, without touching
+ * a device, which route a call without a FORCE flag takes; pyg_hip_spatial_last_route() names what the last call on this
+ * thread ran: "<op> <lane|split> <d4|ldsq|globq> <reg1|reg16|lds|count>[ cosine]".
+ *   lane   one workgroup per tile of 128 queries scans the example's whole candidate range through LDS.
+ *   split  fewer than 256 query tiles (M < 32768: under one workgroup per CU) AND at least 512 candidates per example on
+ *          average: the candidate range is cut into up to 64 chunks, a (tile, chunk) grid leaves sorted partial lists (counts
+ *          for radius) and a second launch merges them by (distance, index).  No atomics: repeated calls give the same bits.
+ * The rule is monotone in M.  PYG_HIP_SPATIAL_FORCE_LANE / _FORCE_SPLIT override it (tests, measurements); forced, the
+ * split route's shortest chunk is 32 candidates instead of 256, so that small inputs span several chunks.
+ * pyg_hip_spatial_tile(which) returns the kernels' tile constants (PYG_HIP_SPATIAL_TILE_*), for tests that probe their edges.
+ */
+#define PYG_SPATIAL_KNN 0
+#define PYG_SPATIAL_RADIUS 1
+#define PYG_SPATIAL_NEAREST 2
+#define PYG_HIP_SPATIAL_FORCE_LANE 1
+#define PYG_HIP_SPATIAL_FORCE_SPLIT 2
+#define PYG_HIP_SPATIAL_COSINE 4
+#define PYG_HIP_SPATIAL_IGNORE_SAME 8
+#define PYG_HIP_SPATIAL_ROUTE_UNSUPPORTED 0
+#define PYG_HIP_SPATIAL_ROUTE_LANE 1
+#define PYG_HIP_SPATIAL_ROUTE_SPLIT 2
+#define PYG_HIP_SPATIAL_TILE_QUERIES 0      /* queries per workgroup */
+#define PYG_HIP_SPATIAL_TILE_CANDIDATES 1   /* candidates per LDS tile, D <= 4 */
+#define PYG_HIP_SPATIAL_TILE_CHUNK_FORCED 2 /* shortest chunk of a forced split */
+#define PYG_HIP_SPATIAL_TILE_ELEMS 3        /* elements per LDS tile, D > 4 (rows = max(1, elems / D)) */
+PYG_HIP_API int pyg_hip_spatial_route(int op, int dtype, int64_t M, int64_t N, int64_t B, int64_t D, int64_t k);
+PYG_HIP_API const char* pyg_hip_spatial_last_route(void);
+PYG_HIP_API int pyg_hip_spatial_tile(int which);
+PYG_HIP_API size_t pyg_hip_spatial_workspace_size(int op, int dtype, int64_t M, int64_t N, int64_t B, int64_t D, int64_t k,
+                                                  int flags);
+PYG_HIP_API int pyg_hip_knn(int dtype, const void* x, int64_t N, const void* y, int64_t M, int64_t D, const int64_t* ptr_x,
+                            const int64_t* ptr_y, int64_t num_examples, int64_t k, int flags, void* workspace,
+                            size_t workspace_bytes, int64_t* num_pairs, void* stream);
+PYG_HIP_API int pyg_hip_knn_emit(int dtype, int64_t N, int64_t M, int64_t D, int64_t num_examples, int64_t k, int flags,
+                                 const void* workspace, size_t workspace_bytes, int64_t num_pairs, int64_t* out, void* stream);
+PYG_HIP_API int pyg_hip_radius(int dtype, const void* x, int64_t N, const void* y, int64_t M, int64_t D, const int64_t* ptr_x,
+                               const int64_t* ptr_y, int64_t num_examples, double r, int64_t max_num_neighbors, int flags,
+                               void* workspace, size_t workspace_bytes, int64_t* num_pairs, void* stream);
+PYG_HIP_API int pyg_hip_radius_emit(int dtype, const void* x, int64_t N, const void* y, int64_t M, int64_t D, const int64_t* ptr_x,
+                                    const int64_t* ptr_y, int64_t num_examples, double r, int64_t max_num_neighbors, int flags,
+                                    void* workspace, size_t workspace_bytes, int64_t num_pairs, int64_t* out, void* stream);
+PYG_HIP_API int pyg_hip_nearest(int dtype, const void* x, int64_t N, const void* y, int64_t M, int64_t D, const int64_t* ptr_x,
+                                const int64_t* ptr_y, int64_t num_examples, int flags, void* workspace, size_t workspace_bytes,
+                                int64_t* out, void* stream);
+PYG_HIP_API int pyg_hip_nearest_pending_error(void);
 
 /* ---- measurement hooks (bench.py) --------------------------------------------------------- */
 

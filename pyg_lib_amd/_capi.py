@@ -12,7 +12,7 @@ _HERE = osp.dirname(osp.abspath(__file__))
 _LIB = None
 
 OK = 0
-ABI_VERSION = 12  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
+ABI_VERSION = 13  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
 DTYPES = {
     torch.float32: 0,
     torch.float64: 1,
@@ -94,6 +94,38 @@ def lib() -> ctypes.CDLL:
         L.pyg_hip_fused_scatter_reduce_backward.argtypes = [c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                                             c.c_int64, c.c_int64, c.c_int64, c.POINTER(c.c_int), c.c_int,
                                                             c.c_void_p, c.c_void_p]
+        # knn / radius / nearest (include/pyg_hip.h, "knn, radius, nearest"); x, y are (pointer, rows) pairs
+        L.pyg_hip_spatial_route.restype = c.c_int
+        L.pyg_hip_spatial_route.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int64]
+        L.pyg_hip_spatial_last_route.restype = c.c_char_p
+        L.pyg_hip_spatial_tile.restype = c.c_int
+        L.pyg_hip_spatial_tile.argtypes = [c.c_int]
+        # (op, dtype, M, N, B, D, k, flags)
+        L.pyg_hip_spatial_workspace_size.restype = c.c_size_t
+        L.pyg_hip_spatial_workspace_size.argtypes = [c.c_int, c.c_int, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int]
+        # (dtype, x, N, y, M, D, ptr_x, ptr_y, num_examples, k, flags, workspace, workspace_bytes, num_pairs, stream)
+        L.pyg_hip_knn.restype = c.c_int
+        L.pyg_hip_knn.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
+                                  c.c_int64, c.c_int64, c.c_int, c.c_void_p, c.c_size_t, c.POINTER(c.c_int64), c.c_void_p]
+        # (dtype, N, M, D, num_examples, k, flags, workspace, workspace_bytes, num_pairs, out, stream)
+        L.pyg_hip_knn_emit.restype = c.c_int
+        L.pyg_hip_knn_emit.argtypes = [c.c_int, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int, c.c_void_p,
+                                       c.c_size_t, c.c_int64, c.c_void_p, c.c_void_p]
+        # (dtype, x, N, y, M, D, ptr_x, ptr_y, num_examples, r, max_num_neighbors, flags, workspace, workspace_bytes, num_pairs, stream)
+        L.pyg_hip_radius.restype = c.c_int
+        L.pyg_hip_radius.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
+                                     c.c_int64, c.c_double, c.c_int64, c.c_int, c.c_void_p, c.c_size_t, c.POINTER(c.c_int64),
+                                     c.c_void_p]
+        # (... as pyg_hip_radius up to workspace_bytes, num_pairs, out, stream)
+        L.pyg_hip_radius_emit.restype = c.c_int
+        L.pyg_hip_radius_emit.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
+                                          c.c_int64, c.c_double, c.c_int64, c.c_int, c.c_void_p, c.c_size_t, c.c_int64,
+                                          c.c_void_p, c.c_void_p]
+        # (dtype, x, N, y, M, D, ptr_x, ptr_y, num_examples, flags, workspace, workspace_bytes, out, stream)
+        L.pyg_hip_nearest.restype = c.c_int
+        L.pyg_hip_nearest.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
+                                      c.c_int64, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+        L.pyg_hip_nearest_pending_error.restype = c.c_int
         _LIB = L
     return _LIB
 
@@ -109,6 +141,9 @@ def binding() -> ctypes.CDLL:
         L.pyg_binding_set_matmul_schedule.restype = None
         L.pyg_binding_set_matmul_schedule.argtypes = [ctypes.c_int]
         L.pyg_binding_get_matmul_schedule.restype = ctypes.c_int
+        L.pyg_binding_set_spatial_route.restype = None
+        L.pyg_binding_set_spatial_route.argtypes = [ctypes.c_int]
+        L.pyg_binding_get_spatial_route.restype = ctypes.c_int
         _BINDING = L
     return _BINDING
 

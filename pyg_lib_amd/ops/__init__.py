@@ -489,6 +489,84 @@ def matmul_f32_split(on: bool = True):
         torch.set_float32_matmul_precision(prev)
 
 
+# ---------------------------------------------------------------------------------------------------
+# knn, radius, nearest (csrc/hip/spatial.hip)
+# ---------------------------------------------------------------------------------------------------
+
+def knn(
+    x: Tensor,
+    y: Tensor,
+    k: int = 1,
+    ptr_x: Optional[Tensor] = None,
+    ptr_y: Optional[Tensor] = None,
+    cosine: bool = False,
+    num_workers: int = 1,
+) -> Tensor:
+    """For every point of ``y`` ``[M, D]`` the ``k`` nearest points of ``x`` ``[N, D]`` inside its example (interface of the
+    reference's ``pyg_lib.ops.knn``; note that ``k`` comes before the pointers here and after them in the operator schema).
+
+    ``ptr_x`` / ``ptr_y`` are int64 CSR pointers of equal length on the points' device; without them there is one example.
+    Returns ``[2, E]`` int64: row 0 the index into ``y``, row 1 the index into ``x``; per query the neighbours are ordered by
+    (squared Euclidean distance, index) and there are ``min(k, candidates)`` of them -- candidates at a NaN or infinite
+    distance do not count.  The distance is summed in fp32 (fp64 for float64 inputs) without fused multiply-add, so HIP and CPU
+    tensors give the same bits.  ``cosine=True`` (device only) uses ``1 - cos``.  On the device ``k <= 100``.  ``num_workers``
+    is accepted and ignored.  Reads the pair count back: one synchronisation of the current stream per call."""
+    return torch.ops.pyg.knn(x, y, ptr_x, ptr_y, k, cosine, num_workers)
+
+
+def radius(
+    x: Tensor,
+    y: Tensor,
+    r: float = 1.0,
+    ptr_x: Optional[Tensor] = None,
+    ptr_y: Optional[Tensor] = None,
+    max_num_neighbors: int = 32,
+    num_workers: int = 1,
+    ignore_same_index: bool = False,
+) -> Tensor:
+    """For every point of ``y`` ``[M, D]`` the points of ``x`` ``[N, D]`` of its example at a distance below ``r`` (strictly:
+    ``dist < r * r``), at most the first ``max_num_neighbors`` in ascending index (interface of the reference's
+    ``pyg_lib.ops.radius``).  Returns ``[2, E]`` int64 ordered by (index into ``y``, index into ``x``) on both devices -- the
+    rule of the reference's CUDA kernel; its CPU kernel returns KD-tree order.  ``ignore_same_index`` drops
+    the pairs ``(i, i)``.  One synchronisation of the current stream per call."""
+    return torch.ops.pyg.radius(x, y, ptr_x, ptr_y, r, max_num_neighbors, num_workers, ignore_same_index)
+
+
+def nearest(
+    x: Tensor,
+    y: Tensor,
+    ptr_x: Optional[Tensor] = None,
+    ptr_y: Optional[Tensor] = None,
+) -> Tensor:
+    """For every point of ``x`` ``[N, D]`` the index of the nearest point of ``y`` ``[M, D]`` inside its example: the first one
+    at the smallest distance (interface of the reference's ``pyg_lib.ops.nearest``).  A point whose example has no candidate
+    at a finite distance gets ``ptr_y[b]`` -- as in the reference; this can equal ``y.size(0)``.  Does not synchronise (and can
+    be captured into a graph): a pointer that decreases or does not end at the row count is clamped, and reported by the NEXT
+    ``nearest`` call on that device."""
+    return torch.ops.pyg.nearest(x, y, ptr_x, ptr_y)
+
+
+def spatial_last_route() -> str:
+    """What the last ``knn`` / ``radius`` / ``nearest`` call made from the calling thread on a HIP device ran:
+    ``'<op> <lane|split> <d4|ldsq|globq> <reg1|reg16|lds|count>[ cosine]'`` (test / diagnostic hook; the rules are in
+    include/pyg_hip.h)."""
+    return _capi.lib().pyg_hip_spatial_last_route().decode()
+
+
+@contextlib.contextmanager
+def spatial_route(route: Optional[str]):
+    """Context manager: the ``knn`` / ``radius`` / ``nearest`` calls of this thread take the ``'lane'`` or the ``'split'``
+    route whatever their sizes (``None``: the library's rule).  For tests and measurements; a forced split uses chunks of
+    at least 32 candidates, so that small inputs span several."""
+    flags = {None: 0, 'lane': 1, 'split': 2}[route]   # PYG_HIP_SPATIAL_FORCE_*
+    prev = _capi.binding().pyg_binding_get_spatial_route()
+    _capi.binding().pyg_binding_set_spatial_route(flags)
+    try:
+        yield
+    finally:
+        _capi.binding().pyg_binding_set_spatial_route(prev)
+
+
 __all__ = [
     'grouped_matmul',
     'segment_matmul',
@@ -497,6 +575,9 @@ __all__ = [
     'sampled_mul',
     'sampled_div',
     'fused_scatter_reduce',
+    'knn',
+    'radius',
+    'nearest',
     'index_sort',
     'scatter',
     'scatter_sum',
