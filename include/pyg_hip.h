@@ -57,6 +57,8 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  14: pyg_hip_matmul_dw_route (which weight-gradient kernel serves a call, asked without running); a host `ptr` of
+ *      pyg_hip_segment_matmul_dw is validated, pyg_hip_matmul_dw_counters count calls that returned PYG_HIP_OK.
  *  13: pyg_hip_knn / _knn_emit, pyg_hip_radius / _radius_emit, pyg_hip_nearest, pyg_hip_spatial_route / _last_route / _tile /
  *      _workspace_size, pyg_hip_nearest_pending_error (batched point-cloud neighbour search).
  *  12: pyg_hip_scatter_route, pyg_hip_scatter_last_route (which kernel serves a scatter call: asked without running, told after).
@@ -72,7 +74,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 13
+#define PYG_HIP_ABI_VERSION 14
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -222,12 +224,14 @@ PYG_HIP_API const char* pyg_hip_matmul_last_variant(void);
  * (input [N, K], grad_out [N, M], grad_other [B, K, M]; fp32 accumulation, one rounding).  Replaces the
  * per-relation loop of SegmentMatmul::backward (ops/autograd/matmul_kernel.cpp:92-107: B x
  * at::matmul(input_i^T, grad_out_i) + at::stack) with one persistent launch.  fp32 / bf16 / fp16, ANY K and M and any
- * element-aligned operands: K in {64, 128, 256} with M % 64 == 0 and 16-byte aligned operands run the shape-specialised
- * kernels of matmul_dw.hip, everything else the general-shape kernel (matmul_dw_gen.hip: 128 x 128 output blocks, tails
- * zero-filled in LDS, widest vector loads the alignment allows).  fp32 multiplies on v_mfma_f32_32x32x2_f32 (IEEE fp32).
- * Other dtypes return PYG_HIP_ERR_UNSUPPORTED (the caller keeps the reference formula).  `workspace`:
- * pyg_hip_segment_matmul_dw_workspace_size(B, K, M) bytes of device scratch (tile plan + fp32 accumulators).  Never
- * synchronises.
+ * element-aligned operands; which kernel runs is the table of pyg_hip_matmul_dw_route below.  fp32 multiplies on
+ * v_mfma_f32_32x32x2_f32 (IEEE fp32).  Other dtypes return PYG_HIP_ERR_UNSUPPORTED (the caller keeps the reference formula).
+ *   ptr        B+1 int64 boundaries, on device if ptr_on_device != 0; a host `ptr` must be non-decreasing within [0, N]
+ *              (PYG_HIP_ERR_INVALID before anything is launched), a device `ptr` is trusted.
+ *   workspace  pyg_hip_segment_matmul_dw_workspace_size(B, K, M) bytes of device scratch (tile plan + fp32 partial slabs).
+ * Checks, in this order: an empty call (B x K x M == 0) returns at once; NULL tensors; dtype; workspace; operands that
+ * are not element-aligned (PYG_HIP_ERR_INVALID); a shape beyond the general kernel (PYG_HIP_ERR_UNSUPPORTED); 2^31 or
+ * more work tiles (PYG_HIP_ERR_INVALID).  Never synchronises.
  */
 PYG_HIP_API size_t pyg_hip_segment_matmul_dw_workspace_size(int64_t B, int64_t K, int64_t M);
 /* Grouped form (the others_grad of GroupedMatmul.backward, pyg_lib/ops/__init__.py:88-94): for every
@@ -236,8 +240,28 @@ PYG_HIP_API size_t pyg_hip_segment_matmul_dw_workspace_size(int64_t B, int64_t K
  * group order (out_i starts at element sum_{j < i} k_j m_j; uniform shapes: one [G, k, m] block).  Workspace:
  * pyg_hip_grouped_matmul_dw_workspace_size(groups, G). */
 PYG_HIP_API size_t pyg_hip_grouped_matmul_dw_workspace_size(const pyg_hip_group* groups, int64_t G);
-/* Diagnostic: calls served by the shape-specialised / the general-shape weight-gradient kernels since the library was
- * loaded (process wide).  Either pointer may be NULL. */
+/*
+ * The route of a weight-gradient call, as a name; launches nothing, touches no device, keeps no state (the returned string
+ * lives in a thread-local buffer until the next query on the thread).  Both entry points take the route this answers.
+ *   uniform   != 0: all groups share (K, M) -- always so for the segment form
+ *   misalign  the low four address bits of every X and dY operand of the call, ORed together, plus the bits of the
+ *             output address below the element size (dW is stored element by element: the output only has to be
+ *             element-aligned)
+ * The first line that applies:
+ *   unsupported           dtype not f32 / bf16 / f16
+ *   invalid               misalign % element size != 0 (or K, M < 0)
+ *   gen                   not uniform, or misalign % 16 != 0, or not (K in {64, 128, 256} and M > 0 and M % 64 == 0): the
+ *                         general-shape kernel (matmul_dw_gen.hip: 128 x 128 output blocks, fp32 128 x 64, tails
+ *                         zero-filled in LDS, widest vector loads the alignment allows) -- but
+ *   unsupported           for such a call with K >= 2^21, M >= 2^21 or K x M >= 2^28 (the kernel's 32-bit offsets)
+ *   wide256_<bf16|f16>    16-bit, K = 256, M % 256 == 0: 256 output columns per workgroup, the waves split the columns
+ *   seg_<t>_k<K>_mc<MC>   everything else, t = bf16 | f16 | f32: every wave owns a K x MC accumulator block, M / MC column
+ *                         chunks per tile range;  K = 64, 128: MC = 128 if M % 128 == 0, else 64;  K = 256: MC = 64
+ *                         (fp32 K = 256 also when M % 256 == 0)
+ */
+PYG_HIP_API const char* pyg_hip_matmul_dw_route(int dtype, int64_t K, int64_t M, int uniform, unsigned misalign);
+/* Diagnostic: calls served by the shape-specialised (seg_*, wide256_*) / the general-shape (gen) weight-gradient kernels
+ * since the library was loaded (process wide); a call counts once it has returned PYG_HIP_OK.  Either pointer may be NULL. */
 PYG_HIP_API void pyg_hip_matmul_dw_counters(int64_t* specialised, int64_t* general);
 PYG_HIP_API int pyg_hip_grouped_matmul_dw(int dtype, const pyg_hip_group* groups, int64_t G, void* out_pool,
                                           void* workspace, size_t workspace_bytes, void* stream);

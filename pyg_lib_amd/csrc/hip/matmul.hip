@@ -505,19 +505,7 @@ int pyg_hip_segment_matmul(int dtype, const void* input, const int64_t* ptr, int
 
   const int64_t* dptr = ptr;
   if (!ptr_on_device) {
-    // ptr lives on the host (the reference's preferred placement): validate, then ship it.
-    for (int64_t b = 0; b < B; ++b)
-      PYG_HIP_REQUIRE(ptr[b + 1] >= ptr[b] && ptr[b] >= 0 && ptr[b + 1] <= N,
-                      "segment_matmul: 'ptr' must be non-decreasing within [0, %lld]",
-                      (long long)N);
-    void* staged = nullptr;
-    int rc = pinned_stage().acquire(sizeof(int64_t) * (size_t)(B + 1), &staged);
-    if (rc != PYG_HIP_OK) return rc;
-    ::memcpy(staged, ptr, sizeof(int64_t) * (size_t)(B + 1));
-    PYG_HIP_CHECK(hipMemcpyAsync(w.ptr_copy, staged, sizeof(int64_t) * (size_t)(B + 1),
-                                 hipMemcpyHostToDevice, stream));
-    rc = pinned_stage().commit(stream);
-    if (rc != PYG_HIP_OK) return rc;
+    if (int rc = stage_host_ptr("segment_matmul", ptr, B, N, w.ptr_copy, stream)) return rc;
     dptr = w.ptr_copy;
   }
   hipLaunchKernelGGL(plan_segments_kernel, dim3(1), dim3(256), 0, stream, dptr, B,

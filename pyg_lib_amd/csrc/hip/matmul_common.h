@@ -2,10 +2,14 @@
 // units of segment_matmul / grouped_matmul, and the launch functions through which matmul.hip (tile tables, route choice,
 // entry points) reaches the kernel families: matmul_lds.hip (W in LDS, contiguous tile ranges), matmul_f32_pipe.hip
 // (fp32 K = 128), matmul_k128.hip (16-bit K = M = 128: cyclic / ticket schedules), matmul_k256.hip (16-bit K = 256, 256
-// columns per workgroup), matmul_ring.hip (item rings), matmul_gen.hip (general shapes).
+// columns per workgroup), matmul_ring.hip (item rings), matmul_gen.hip (general shapes).  The weight gradient has the same shape: matmul_dw.hip
+// (plan, workspace layout, route choice, entry points, the shape-specialised kernels) reaches matmul_dw_gen.hip (general
+// shapes) through launch_dw_gen; the descriptors of both and the host-`ptr` staging of all entry points are declared here.
 #pragma once
 
 #include "common.h"
+
+#include <string.h>
 
 #include <algorithm>
 
@@ -41,6 +45,29 @@ struct DevGroup {
   int32_t trans;
   int32_t pad;
 };
+
+// Weight gradient, shape-specialised kernels: `rows` rows of X [rows, K] and dY [rows, M] (row-major, M = row pitch of dY).
+struct DwGroup {
+  const uint16_t* x;
+  const uint16_t* dy;
+  int64_t rows;
+};
+
+// Weight gradient, general-shape kernel.
+struct DwGenGroup {  // 48 bytes
+  const char* x;     // [rows, k] row-major
+  const char* dy;    // [rows, m] row-major
+  int64_t rows;
+  int64_t acc_off;   // first element of this group's [k, m] block in the fp32 image (and in the output pool)
+  int32_t k, m;
+  int16_t lx, ly;    // log2 of the vector bytes the X / dY rows may be fetched with (1 ... 4)
+  int16_t nkb, nmb;  // blocks along k and m
+};
+static_assert(sizeof(DwGenGroup) == 48, "DwGenGroup layout");
+
+// Output block of the general-shape weight-gradient kernel: 128 x 128 entries, 128 x 64 for 4-byte elements.
+constexpr int kDwGenKB = 128;
+constexpr int dw_gen_mb(int elt) { return elt == 4 ? 64 : 128; }
 
 template <typename T>
 struct Elem;
@@ -201,6 +228,21 @@ inline unsigned tile_grid(int64_t tiles_upper, int per_cu, int ncol = 1) {
   return (unsigned)(gx * ncol);
 }
 
+// A `ptr` that lives on the host (the reference's preferred placement): validated -- B + 1 non-decreasing boundaries
+// within [0, N] --, then shipped to `ptr_dev` through the pinned stage.  `op` names the entry point in the message.
+inline int stage_host_ptr(const char* op, const int64_t* ptr, int64_t B, int64_t N, int64_t* ptr_dev, hipStream_t stream) {
+  for (int64_t b = 0; b < B; ++b)
+    PYG_HIP_REQUIRE(ptr[b + 1] >= ptr[b] && ptr[b] >= 0 && ptr[b + 1] <= N, "%s: 'ptr' must be non-decreasing within [0, %lld]",
+                    op, (long long)N);
+  const size_t bytes = sizeof(int64_t) * (size_t)(B + 1);
+  void* staged = nullptr;
+  int rc = pinned_stage().acquire(bytes, &staged);
+  if (rc != PYG_HIP_OK) return rc;
+  ::memcpy(staged, ptr, bytes);
+  PYG_HIP_CHECK(hipMemcpyAsync(ptr_dev, staged, bytes, hipMemcpyHostToDevice, stream));
+  return pinned_stage().commit(stream);
+}
+
 }  // namespace
 
 // The launch functions below take the device descriptors, the tile prefix their kernel walks (`tile_start`: 128-row
@@ -232,12 +274,10 @@ int launch_matmul_gen(int dtype, const void* descs, const int32_t* tile_start, i
 int launch_ring_k256(int dtype, const void* descs, const int32_t* tile_start3, int B, int64_t tiles3_upper, hipStream_t stream);
 int launch_ring_k128(int dtype, const void* descs, const int32_t* tile_start3, int B, int64_t tiles3_upper, hipStream_t stream);
 int launch_ring_f32x3(const void* descs, const int32_t* tile_start3, int B, int64_t tiles3_upper, hipStream_t stream);
-// matmul_dw_gen.hip: the general-shape weight gradient (per-group K, M, alignment class; bf16 / f16 / f32).  The
-// workspace is carved as [B + 1 ptr copy][descriptors][tile prefix][two fp32 partial slabs per workgroup].
-size_t dw_gen_workspace_bytes(int64_t B);
-int dw_gen_segment(int dtype, const void* input, const int64_t* ptr, int ptr_on_device, const void* grad_out,
-                   void* grad_other, int64_t N, int64_t K, int64_t M, int64_t B, void* workspace, hipStream_t stream);
-int dw_gen_grouped(int dtype, const pyg_hip_group* host_groups, int64_t G, void* out_pool, void* workspace,
-                   hipStream_t stream);
+// matmul_dw_gen.hip: the general-shape weight gradient (per-group K, M, alignment class; bf16 / f16 / f32).  `descs`:
+// DwGenGroup[B] cut for blocks of kDwGenKB x dw_gen_mb(element size); `gx` main workgroups, each with two fp32 slabs of one
+// block in `slabs`; `lg`: alignment class of the launch = the smallest over its groups' operands (log2 of the vector bytes).
+int launch_dw_gen(int dtype, const void* descs, const int32_t* tile_start, int B, int64_t gx, float* slabs, void* out, int lg,
+                  hipStream_t stream);
 
 }  // namespace pyg_hip

@@ -21,11 +21,15 @@
 //     fixed order; a relation that lies inside the workgroup's range is rounded and stored at once, the (at most two)
 //     partial ones per workgroup go to fp32 slabs that a small fix-up launch adds in workgroup order.  dW is the same
 //     bits in every run, like the reference's per-relation at::matmul.
+//
+// This file is also the dispatch of the weight gradient, as matmul.hip is for the forward: behind the kernels follow the plan
+// (dw_describe / dw_plan_kernel: ptr or host groups -> descriptors + tile prefix), the route (choose_dw_route: the table
+// of pyg_hip_matmul_dw_route in pyg_hip.h, the one place that decides which kernel a (dtype, K, M, alignment) runs), what
+// follows from a route (grid, slab size, workspace layout: carve_dw), run_dw_route and the C entry points.  The
+// general-shape kernel lives in matmul_dw_gen.hip behind launch_dw_gen (matmul_common.h).
 #include "matmul_dw_out.h"
 
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <atomic>
@@ -72,52 +76,6 @@ constexpr int pitch_bytes(int cols) {
 // global_* loads (the descriptors hold generic pointers: through them the compiler emits flat_* accesses, which also count
 // on lgkmcnt -- every LDS wait then waits for the rows in flight as well)
 typedef const __attribute__((address_space(1))) u32x4 GU32x4;
-
-// One relation / group: `rows` rows of X [rows, K] and dY [rows, M] (row-major, M = row pitch of dY).
-struct DwGroup {
-  const uint16_t* x;
-  const uint16_t* dy;
-  int64_t rows;
-};
-
-// segment form: descriptors + tile prefix from ptr; tile_start[b] = sum_{b' < b} ceil(rows_b' / 128)
-__global__ void dw_plan_kernel(const int64_t* __restrict__ ptr, int64_t B, const uint16_t* X, const uint16_t* dY,
-                               int64_t K, int64_t M, DwGroup* __restrict__ groups,
-                               int32_t* __restrict__ tile_start) {
-  __shared__ int64_t part[256];
-  const int tid = threadIdx.x;
-  const int64_t per = (B + 255) / 256;
-  const int64_t beg = min((int64_t)tid * per, B), end = min(beg + per, B);
-  int64_t t = 0;
-  for (int64_t b = beg; b < end; ++b) {
-    const int64_t r = ptr[b + 1] - ptr[b];
-    t += r > 0 ? (r + kTile - 1) / kTile : 0;
-  }
-  part[tid] = t;
-  __syncthreads();
-  if (tid == 0) {
-    int64_t acc = 0;
-    for (int i = 0; i < 256; ++i) {
-      const int64_t v = part[i];
-      part[i] = acc;
-      acc += v;
-    }
-    tile_start[B] = (int32_t)acc;
-  }
-  __syncthreads();
-  t = part[tid];
-  for (int64_t b = beg; b < end; ++b) {
-    tile_start[b] = (int32_t)t;
-    const int64_t p0 = ptr[b];
-    const int64_t r = ptr[b + 1] - p0;
-    DwGroup d;
-    d.x = X + p0 * K;
-    d.dy = dY + p0 * M;
-    d.rows = r > 0 ? r : 0;
-    groups[b] = d;
-    t += r > 0 ? (r + kTile - 1) / kTile : 0;
-  }
-}
 
 template <typename Tag, int K, int MC>
 __global__ __launch_bounds__(256, 1) void seg_dw_kernel(const DwGroup* __restrict__ groups,
@@ -624,134 +582,351 @@ __global__ __launch_bounds__(256) void seg_dw_fixup_kernel(const int32_t* __rest
   dw_quarter_to_out<Pos>(out + (int64_t)lo * K * M + by * MC, M, K, MC, bt, q, s, lane);
 }
 
-inline size_t dw_groups_bytes(int64_t B) { return align_up(sizeof(DwGroup) * (size_t)(B > 0 ? B : 1), 256); }
-inline size_t dw_tiles_bytes(int64_t B) { return align_up(sizeof(int32_t) * (size_t)(B + 1), 256); }
-
-// column chunk of the kernel a (dtype, K, M) runs (run_dw / run_dw_f32 below) and the grid it gets
-inline int dw_mc(bool f32, int64_t K, int64_t M) {
-  if (!f32 && K == 256 && M % 256 == 0) return 256;
-  if (K == 256) return 64;
-  return M % 128 == 0 ? 128 : 64;
+// ---- plan: descriptors + tile prefix ---------------------------------------------------------------
+// The descriptor of one group for the kernel that will walk it.  Returns the work tiles per 128-row tile of the group: 1 for
+// the shape-specialised kernels (their column chunks are workgroups, not tiles), the number of kb x mb blocks of the
+// [k, m] output for the general-shape kernel.  Shared by the plan kernel (segment form) and the host loop (grouped form).
+__host__ __device__ inline int64_t dw_describe(DwGroup& d, const char* x, const char* dy, int64_t rows, int64_t, int64_t, int,
+                                               int64_t, int, int) {
+  d.x = reinterpret_cast<const uint16_t*>(x);
+  d.dy = reinterpret_cast<const uint16_t*>(dy);
+  d.rows = rows;
+  return 1;
 }
+__host__ __device__ inline int64_t dw_describe(DwGenGroup& d, const char* x, const char* dy, int64_t rows, int64_t k, int64_t m,
+                                               int elt, int64_t acc_off, int kb, int mb) {
+  auto mn = [](int a, int b) { return a < b ? a : b; };
+  d.x = x;
+  d.dy = dy;
+  d.rows = rows;
+  d.acc_off = acc_off;
+  d.k = (int32_t)k;
+  d.m = (int32_t)m;
+  d.lx = (int16_t)mn(gen_log2_align((uint64_t)x), gen_log2_align((uint64_t)(k * elt)));
+  d.ly = (int16_t)mn(gen_log2_align((uint64_t)dy), gen_log2_align((uint64_t)(m * elt)));
+  d.nkb = (int16_t)((k + kb - 1) / kb);
+  d.nmb = (int16_t)((m + mb - 1) / mb);
+  return (int64_t)d.nkb * d.nmb;
+}
+
+// segment form: descriptors + tile prefix from ptr (uniform K, M; one thread per run of relations);
+// tile_start[b] = sum_{b' < b} ceil(rows_b' / 128) * (work tiles per row tile)
+template <typename Desc>
+__global__ void dw_plan_kernel(const int64_t* __restrict__ ptr, int64_t B, const char* X, const char* dY, int64_t K, int64_t M,
+                               int elt, int kb, int mb, Desc* __restrict__ groups, int32_t* __restrict__ tile_start) {
+  __shared__ int64_t part[256];
+  const int tid = threadIdx.x;
+  const int64_t per = (B + 255) / 256;
+  const int64_t beg = min((int64_t)tid * per, B), end = min(beg + per, B);
+  Desc d;
+  const int64_t blocks = dw_describe(d, X, dY, 0, K, M, elt, 0, kb, mb);
+  int64_t t = 0;
+  for (int64_t b = beg; b < end; ++b) {
+    const int64_t r = ptr[b + 1] - ptr[b];
+    t += r > 0 ? (r + kTile - 1) / kTile * blocks : 0;
+  }
+  part[tid] = t;
+  __syncthreads();
+  if (tid == 0) {
+    int64_t acc = 0;
+    for (int i = 0; i < 256; ++i) {
+      const int64_t v = part[i];
+      part[i] = acc;
+      acc += v;
+    }
+    tile_start[B] = (int32_t)acc;
+  }
+  __syncthreads();
+  t = part[tid];
+  for (int64_t b = beg; b < end; ++b) {
+    tile_start[b] = (int32_t)t;
+    const int64_t p0 = ptr[b];
+    const int64_t r = ptr[b + 1] - p0;
+    dw_describe(d, X + p0 * K * elt, dY + p0 * M * elt, r > 0 ? r : 0, K, M, elt, b * K * M, kb, mb);
+    groups[b] = d;
+    t += r > 0 ? (r + kTile - 1) / kTile * blocks : 0;
+  }
+}
+
+// ---- the route: which kernel serves a call ---------------------------------------------------------
+enum class DwFamily {
+  kUnsupported,  // no kernel for the dtype, or a shape beyond the general kernel's 32-bit offsets
+  kInvalid,      // an operand that is not element-aligned
+  kGen,          // matmul_dw_gen.hip: K x MC = its output block
+  kSeg,          // seg_dw_kernel / seg_dw_f32_kernel<K, MC>
+  kWide256,      // seg_dw_wide256_kernel
+};
+struct DwRoute {
+  DwFamily family;
+  int K = 0, MC = 0;  // contraction length and output columns of one accumulator set (kGen: of one block)
+};
+
+inline bool dw_dtype_ok(int dtype) { return dtype == PYG_F32 || dtype == PYG_BF16 || dtype == PYG_F16; }
+inline int dw_elt(int dtype) { return dtype == PYG_F32 ? 4 : 2; }
+inline DwRoute dw_gen_route(int dtype) { return {DwFamily::kGen, kDwGenKB, dw_gen_mb(dw_elt(dtype))}; }
+
+// The route of a call: the table of pyg_hip_matmul_dw_route in pyg_hip.h.  `uniform`: all groups share (K, M); `misalign`:
+// dw_misalign() of the call.  Pure: no HIP call, no global, no device property.
+DwRoute choose_dw_route(int dtype, int64_t K, int64_t M, bool uniform, unsigned misalign) {
+  if (!dw_dtype_ok(dtype)) return {DwFamily::kUnsupported};
+  if (misalign % dw_elt(dtype) != 0) return {DwFamily::kInvalid};
+  if (!uniform || misalign % 16 != 0 || !((K == 64 || K == 128 || K == 256) && M > 0 && M % 64 == 0)) {
+    if (K >= (1LL << 21) || M >= (1LL << 21) || K * M >= (1LL << 28)) return {DwFamily::kUnsupported};
+    return dw_gen_route(dtype);
+  }
+  // 16-bit K = 256: the waves split the columns of a 256-wide chunk instead of the rows (X and dY pass through one CU once)
+  if (dtype != PYG_F32 && K == 256 && M % 256 == 0) return {DwFamily::kWide256, 256, 256};
+  // a wave's K x MC accumulator block has to fit its 256 accumulation registers
+  return {DwFamily::kSeg, (int)K, K == 256 || M % 128 != 0 ? 64 : 128};
+}
+
+// `misalign` of a call: the low four address bits of all its X and dY operands (`operands`: their addresses ORed), and of the
+// output the bits below the element size -- dW is stored element by element, so it only has to be element-aligned.
+inline unsigned dw_misalign(uintptr_t operands, const void* out, int elt) {
+  return (unsigned)((operands & 15) | ((uintptr_t)out & (uintptr_t)(elt - 1)));
+}
+
+const char* dw_route_name(int dtype, DwRoute r) {
+  thread_local char name[32];
+  const char* t = dtype == PYG_BF16 ? "bf16" : dtype == PYG_F16 ? "f16" : "f32";
+  switch (r.family) {
+    case DwFamily::kUnsupported: return "unsupported";
+    case DwFamily::kInvalid: return "invalid";
+    case DwFamily::kGen: return "gen";
+    case DwFamily::kSeg: snprintf(name, sizeof(name), "seg_%s_k%d_mc%d", t, r.K, r.MC); break;
+    case DwFamily::kWide256: snprintf(name, sizeof(name), "wide256_%s", t); break;
+  }
+  return name;
+}
+
+// A route that cannot run, as the error of entry point `op` for a group of shape (K, M).
+int dw_route_check(const char* op, DwRoute r, int64_t K, int64_t M) {
+  if (r.family == DwFamily::kInvalid) return fail(PYG_HIP_ERR_INVALID, "%s: operands must be element-aligned", op);
+  if (r.family == DwFamily::kUnsupported)
+    return fail(PYG_HIP_ERR_UNSUPPORTED, "%s: K x M = %lld x %lld is beyond the kernel's 32-bit offsets", op, (long long)K,
+                (long long)M);
+  if (r.family == DwFamily::kGen)  // DwGenGroup::nkb, nmb
+    PYG_HIP_REQUIRE((K + r.K - 1) / r.K < 32768 && (M + r.MC - 1) / r.MC < 32768, "%s: K / M too large", op);
+  return PYG_HIP_OK;
+}
+
+// ---- what follows from the route: grid, slabs, workspace ------------------------------------------
+// column-chunk workgroups per tile range
+inline int64_t dw_ncol(DwRoute r, int64_t M) { return r.family == DwFamily::kGen ? 1 : M / r.MC; }
+// tile ranges (= main workgroups / ncol) of a call with at most `tiles_upper` tiles
 inline int64_t dw_grid_x(int64_t tiles_upper, int64_t ncol) {
   int64_t gx = std::max<int64_t>(1, std::min<int64_t>(tiles_upper, device_info().num_cus / ncol));
   if (ncol > 1) gx = (gx + 7) / 8 * 8;  // the kernels' XCD-aware decode works on groups of 8 ids
   return gx;
 }
-// two fp32 slabs of K x MC per main workgroup; the bound holds for every tile count and for both the 16-bit and the
-// fp32 kernel of the shape
-inline size_t dw_slab_bytes(int64_t K, int64_t M) {
-  if (!((K == 64 || K == 128 || K == 256) && M > 0 && M % 64 == 0)) return 0;  // (dw_fast_shape: the other shapes run matmul_dw_gen.hip)
-  size_t worst = 0;
-  for (int f32 = 0; f32 < 2; ++f32) {
-    const int64_t mc = dw_mc(f32 != 0, K, M), ncol = M / mc;
-    const int64_t gx = dw_grid_x(INT64_MAX, ncol);
-    worst = std::max(worst, (size_t)(gx * ncol) * 2 * (size_t)K * (size_t)mc * sizeof(float));
-  }
-  return worst;
-}
-inline size_t dw_ws_bytes(int64_t B, int64_t K, int64_t M) {
-  return align_up(sizeof(int64_t) * (size_t)(B + 1), 256) + dw_groups_bytes(B) + dw_tiles_bytes(B) + dw_slab_bytes(K, M);
+// two fp32 slabs of K x MC per main workgroup; the bound holds for every tile count
+inline size_t dw_slab_bytes(DwRoute r, int64_t M) {
+  const int64_t ncol = dw_ncol(r, M);
+  return (size_t)(dw_grid_x(INT64_MAX, ncol) * ncol) * 2 * (size_t)r.K * (size_t)r.MC * sizeof(float);
 }
 
+struct DwWorkspace {
+  int64_t* ptr_copy;    // B + 1 (segment form with a host `ptr`)
+  void* descs;          // DwGroup / DwGenGroup [B]
+  int32_t* tile_start;  // B + 1, directly behind the descriptors: the grouped form ships both in one copy
+  float* slabs;
+  size_t plan_bytes;    // descriptors + tile prefix
+  size_t bytes;         // of the whole layout
+};
+
+// The workspace layout: `ws` (may be null: size query) cut into the arrays above; DwWorkspace::bytes = what the cut needs.
+DwWorkspace carve_dw(void* ws, int64_t B, size_t desc_size, size_t slab_bytes) {
+  DwWorkspace w;
+  size_t off = 0;
+  auto take = [&](size_t bytes, size_t align) {
+    void* p = reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(ws) + off);
+    off += align_up(bytes, align);
+    return p;
+  };
+  w.ptr_copy = static_cast<int64_t*>(take(sizeof(int64_t) * (size_t)(B + 1), 256));
+  w.descs = take(desc_size * (size_t)std::max<int64_t>(B, 1), 256);
+  w.tile_start = static_cast<int32_t*>(take(sizeof(int32_t) * (size_t)(B + 1), 256));
+  w.plan_bytes = off - (size_t)(static_cast<char*>(w.descs) - static_cast<char*>(ws));
+  w.slabs = static_cast<float*>(take(slab_bytes, 1));
+  w.bytes = off;
+  return w;
+}
+DwWorkspace carve_dw(void* ws, int64_t B, DwRoute r, int64_t M) {
+  return carve_dw(ws, B, r.family == DwFamily::kGen ? sizeof(DwGenGroup) : sizeof(DwGroup), dw_slab_bytes(r, M));
+}
+
+// Bytes for B groups of shape (K, M): the size queries know neither dtype nor alignment, so this is the largest layout over
+// the routes the shape can take.
+size_t dw_workspace_bytes(int64_t B, int64_t K, int64_t M, bool uniform) {
+  size_t need = 0;
+  for (int dtype : {PYG_BF16, PYG_F32}) {
+    need = std::max(need, carve_dw(nullptr, B, dw_gen_route(dtype), M).bytes);
+    const DwRoute r = choose_dw_route(dtype, K, M, uniform, 0);
+    if (r.family == DwFamily::kSeg || r.family == DwFamily::kWide256) need = std::max(need, carve_dw(nullptr, B, r, M).bytes);
+  }
+  return need;
+}
+
+// ---- launches -------------------------------------------------------------------------------------------
+struct DwLaunch {
+  const DwGroup* groups;
+  const int32_t* tile_start;
+  int64_t B, M;
+  int64_t gx;  // tile ranges
+  float* slabs;
+  void* out;
+  hipStream_t stream;
+};
+
 template <typename Pos, typename OutT>
-int launch_fixup(const int32_t* tile_start, int64_t B, int64_t K, int64_t M, int MC, int64_t gx, const float* slabs,
-                 OutT* out, hipStream_t stream) {
-  const int64_t ncol = M / MC;
-  const int64_t fix_blocks = gx * ncol * Pos::kBlocks;  // 4 NBT waves per main workgroup, 4 waves per block
-  hipLaunchKernelGGL((seg_dw_fixup_kernel<Pos, OutT>), dim3((unsigned)(fix_blocks + B)), dim3(256), 0, stream, tile_start,
-                     (int)B, (int)K, (int)M, MC, (int)gx, (int)fix_blocks, slabs, out);
+int launch_fixup(const DwLaunch& a, int K, int MC, OutT* out) {
+  const int64_t ncol = a.M / MC;
+  const int64_t fix_blocks = a.gx * ncol * Pos::kBlocks;  // 4 NBT waves per main workgroup, 4 waves per block
+  hipLaunchKernelGGL((seg_dw_fixup_kernel<Pos, OutT>), dim3((unsigned)(fix_blocks + a.B)), dim3(256), 0, a.stream, a.tile_start,
+                     (int)a.B, K, (int)a.M, MC, (int)a.gx, (int)fix_blocks, a.slabs, out);
   PYG_HIP_CHECK(hipGetLastError());
   return PYG_HIP_OK;
 }
 
 template <typename Tag, int K, int MC>
-int launch_dw(const DwGroup* groups, const int32_t* tile_start, int64_t B, int64_t M, int64_t tiles_upper, float* slabs,
-              void* out_, hipStream_t stream) {
+int launch_dw(const DwLaunch& a) {
   using OutT = typename OutOf<Tag>::type;
-  OutT* out = static_cast<OutT*>(out_);
+  OutT* out = static_cast<OutT*>(a.out);
   constexpr int lds = 4 * 32 * (pitch_bytes(K) + pitch_bytes(MC));
   static_assert(lds >= (K / 32) * (MC / 32) * 4096, "the combine area must fit the row images");
   const void* kern = reinterpret_cast<const void*>(&seg_dw_kernel<Tag, K, MC>);
   if (int rc_ = ensure_dynamic_lds(kern, lds)) return rc_;
-  const int64_t ncol = M / MC;
-  const int64_t gx = dw_grid_x(tiles_upper, ncol);
-  hipLaunchKernelGGL((seg_dw_kernel<Tag, K, MC>), dim3((unsigned)(gx * ncol)), dim3(256), lds, stream, groups,
-                     tile_start, (int)B, (int)M, slabs, out);
+  hipLaunchKernelGGL((seg_dw_kernel<Tag, K, MC>), dim3((unsigned)(a.gx * (a.M / MC))), dim3(256), lds, a.stream, a.groups,
+                     a.tile_start, (int)a.B, (int)a.M, a.slabs, out);
   PYG_HIP_CHECK(hipGetLastError());
-  return launch_fixup<DwPosRows<K / 32, MC / 32>, OutT>(tile_start, B, K, M, MC, gx, slabs, out, stream);
+  return launch_fixup<DwPosRows<K / 32, MC / 32>, OutT>(a, K, MC, out);
 }
 
 template <typename Tag>
-int launch_dw_wide256(const DwGroup* groups, const int32_t* tile_start, int64_t B, int64_t M, int64_t tiles_upper,
-                      float* slabs, void* out_, hipStream_t stream) {
+int launch_dw_wide256(const DwLaunch& a) {
   using OutT = typename OutOf<Tag>::type;
-  OutT* out = static_cast<OutT*>(out_);
+  OutT* out = static_cast<OutT*>(a.out);
   constexpr int lds = 2 * 32 * (pitch_bytes(256) + pitch_bytes(256)) + 4 * 16384;  // two images + the flush staging area
   const void* kern = reinterpret_cast<const void*>(&seg_dw_wide256_kernel<Tag>);
   if (int rc_ = ensure_dynamic_lds(kern, lds)) return rc_;
-  const int64_t ncol = M / 256;
-  const int64_t gx = dw_grid_x(tiles_upper, ncol);
-  hipLaunchKernelGGL((seg_dw_wide256_kernel<Tag>), dim3((unsigned)(gx * ncol)), dim3(256), lds, stream, groups, tile_start,
-                     (int)B, (int)M, slabs, out);
+  hipLaunchKernelGGL((seg_dw_wide256_kernel<Tag>), dim3((unsigned)(a.gx * (a.M / 256))), dim3(256), lds, a.stream, a.groups,
+                     a.tile_start, (int)a.B, (int)a.M, a.slabs, out);
   PYG_HIP_CHECK(hipGetLastError());
-  return launch_fixup<DwPosWide, OutT>(tile_start, B, 256, M, 256, gx, slabs, out, stream);
-}
-
-template <typename Tag>
-int run_dw(const DwGroup* groups, const int32_t* tile_start, int64_t B, int64_t K, int64_t M, int64_t tiles_upper,
-           float* slabs, void* out, hipStream_t stream) {
-  if (K == 256 && M % 256 == 0) return launch_dw_wide256<Tag>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  if (K == 128 && M % 128 == 0) return launch_dw<Tag, 128, 128>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  if (K == 128 && M % 64 == 0) return launch_dw<Tag, 128, 64>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  if (K == 64 && M % 128 == 0) return launch_dw<Tag, 64, 128>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  if (K == 64 && M % 64 == 0) return launch_dw<Tag, 64, 64>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  if (K == 256 && M % 64 == 0) return launch_dw<Tag, 256, 64>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  return fail(PYG_HIP_ERR_UNSUPPORTED, "segment_matmul_dw: K=%lld, M=%lld has no MFMA kernel (K in {64,128,256}, M %% 64 == 0)",
-              (long long)K, (long long)M);
+  return launch_fixup<DwPosWide, OutT>(a, 256, 256, out);
 }
 
 template <int K, int MC>
-int launch_dw_f32(const DwGroup* groups, const int32_t* tile_start, int64_t B, int64_t M, int64_t tiles_upper, float* slabs,
-                  void* out_, hipStream_t stream) {
-  float* out = static_cast<float*>(out_);
+int launch_dw_f32(const DwLaunch& a) {
+  float* out = static_cast<float*>(a.out);
   constexpr int lds = (K / 32) * (MC / 32) * 4096;  // the waves' combine area
   const void* kern = reinterpret_cast<const void*>(&seg_dw_f32_kernel<K, MC>);
   if (int rc_ = ensure_dynamic_lds(kern, lds)) return rc_;
-  const int64_t ncol = M / MC;
-  const int64_t gx = dw_grid_x(tiles_upper, ncol);
-  hipLaunchKernelGGL((seg_dw_f32_kernel<K, MC>), dim3((unsigned)(gx * ncol)), dim3(256), lds, stream, groups, tile_start,
-                     (int)B, (int)M, slabs, out);
+  hipLaunchKernelGGL((seg_dw_f32_kernel<K, MC>), dim3((unsigned)(a.gx * (a.M / MC))), dim3(256), lds, a.stream, a.groups,
+                     a.tile_start, (int)a.B, (int)a.M, a.slabs, out);
   PYG_HIP_CHECK(hipGetLastError());
-  return launch_fixup<DwPosF32<K / 32, MC / 32>, float>(tile_start, B, K, M, MC, gx, slabs, out, stream);
+  return launch_fixup<DwPosF32<K / 32, MC / 32>, float>(a, K, MC, out);
 }
 
-int run_dw_f32(const DwGroup* groups, const int32_t* tile_start, int64_t B, int64_t K, int64_t M, int64_t tiles_upper,
-               float* slabs, void* out, hipStream_t stream) {
-  if (K == 128 && M % 128 == 0) return launch_dw_f32<128, 128>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  if (K == 128 && M % 64 == 0) return launch_dw_f32<128, 64>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  if (K == 64 && M % 128 == 0) return launch_dw_f32<64, 128>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  if (K == 64 && M % 64 == 0) return launch_dw_f32<64, 64>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  if (K == 256 && M % 64 == 0) return launch_dw_f32<256, 64>(groups, tile_start, B, M, tiles_upper, slabs, out, stream);
-  return fail(PYG_HIP_ERR_UNSUPPORTED, "segment_matmul_dw: K=%lld, M=%lld has no MFMA kernel (K in {64,128,256}, M %% 64 == 0)",
-              (long long)K, (long long)M);
+template <int K, int MC>
+int launch_seg(int dtype, const DwLaunch& a) {
+  return dtype == PYG_F32 ? launch_dw_f32<K, MC>(a) : dtype == PYG_BF16 ? launch_dw<bf16_tag, K, MC>(a) : launch_dw<f16_tag, K, MC>(a);
 }
 
-// shapes of the specialised kernels above; everything else (and operands that are not 16-byte aligned) runs
-// matmul_dw_gen.hip
-inline bool dw_fast_shape(int64_t K, int64_t M) { return (K == 64 || K == 128 || K == 256) && M > 0 && M % 64 == 0; }
+// Launch the kernel of route `r` on the planned workspace.  `tiles_upper`: upper bound of the call's tiles; `lg`: alignment
+// class of the call's operands (general route).
+int run_dw_route(DwRoute r, int dtype, const DwWorkspace& w, int64_t B, int64_t M, int64_t tiles_upper, void* out, int lg,
+                 hipStream_t stream) {
+  const int64_t gx = dw_grid_x(tiles_upper, dw_ncol(r, M));
+  const DwLaunch a = {static_cast<const DwGroup*>(w.descs), w.tile_start, B, M, gx, w.slabs, out, stream};
+  switch (r.family) {
+    case DwFamily::kGen: return launch_dw_gen(dtype, w.descs, w.tile_start, (int)B, gx, w.slabs, out, lg, stream);
+    case DwFamily::kWide256: return dtype == PYG_BF16 ? launch_dw_wide256<bf16_tag>(a) : launch_dw_wide256<f16_tag>(a);
+    case DwFamily::kSeg:
+      if (r.K == 128 && r.MC == 128) return launch_seg<128, 128>(dtype, a);
+      if (r.K == 128 && r.MC == 64) return launch_seg<128, 64>(dtype, a);
+      if (r.K == 64 && r.MC == 128) return launch_seg<64, 128>(dtype, a);
+      if (r.K == 64 && r.MC == 64) return launch_seg<64, 64>(dtype, a);
+      if (r.K == 256 && r.MC == 64) return launch_seg<256, 64>(dtype, a);
+      break;
+    default: break;
+  }
+  return fail(PYG_HIP_ERR_INVALID, "matmul_dw: unknown route");
+}
+
+// launches served by the shape-specialised / the general-shape kernels since the library was loaded (tests assert that a
+// backward pass ran a device kernel and not the caller's fallback formula; the backward runs on an autograd thread, so a
+// thread-local "last route" would not be visible to the test)
+std::atomic<int64_t> g_dw_fast{0}, g_dw_gen{0};
+inline int dw_count(DwRoute r, int rc) {
+  if (rc == PYG_HIP_OK) ++(r.family == DwFamily::kGen ? g_dw_gen : g_dw_fast);
+  return rc;
+}
+
+// segment form on a checked route: plan on the device from `ptr`, then the route's kernel
+template <typename Desc>
+int dw_segment(DwRoute r, int dtype, const void* input, const int64_t* ptr, int ptr_on_device, const void* grad_out,
+               void* grad_other, int64_t N, int64_t K, int64_t M, int64_t B, void* workspace, hipStream_t stream) {
+  const int elt = dw_elt(dtype);
+  const char* X = static_cast<const char*>(input);
+  const char* dY = static_cast<const char*>(grad_out);
+  Desc d;
+  const int64_t tiles_upper = ((N + kTile - 1) / kTile + B) * dw_describe(d, X, dY, 0, K, M, elt, 0, r.K, r.MC);
+  PYG_HIP_REQUIRE(tiles_upper < (1LL << 31), "segment_matmul_dw: too many tiles");
+  const DwWorkspace w = carve_dw(workspace, B, r, M);
+  const int64_t* dptr = ptr;
+  if (!ptr_on_device) {
+    if (int rc = stage_host_ptr("segment_matmul_dw", ptr, B, N, w.ptr_copy, stream)) return rc;
+    dptr = w.ptr_copy;
+  }
+  hipLaunchKernelGGL(dw_plan_kernel<Desc>, dim3(1), dim3(256), 0, stream, dptr, B, X, dY, K, M, elt, r.K, r.MC,
+                     static_cast<Desc*>(w.descs), w.tile_start);
+  PYG_HIP_CHECK(hipGetLastError());
+  // a relation starts ptr[b] rows into the tensors: its alignment is at least that of the base and the row pitch
+  const int lg = gen_log2_align((uint64_t)input | (uint64_t)(K * elt) | (uint64_t)grad_out | (uint64_t)(M * elt));
+  return run_dw_route(r, dtype, w, B, M, tiles_upper, grad_other, lg, stream);
+}
+
+// grouped form on a checked route: plan on the host (G is small) -- descriptors + tile prefix in one pinned H2D copy --,
+// then the route's kernel
+template <typename Desc>
+int dw_grouped(DwRoute r, int dtype, const pyg_hip_group* host_groups, int64_t G, void* out_pool, void* workspace,
+               hipStream_t stream) {
+  const int elt = dw_elt(dtype);
+  const DwWorkspace w = carve_dw(workspace, G, r, host_groups[0].m);
+  void* staged = nullptr;
+  int rc = pinned_stage().acquire(w.plan_bytes, &staged);
+  if (rc != PYG_HIP_OK) return rc;
+  Desc* hd = static_cast<Desc*>(staged);
+  int32_t* ht = reinterpret_cast<int32_t*>(static_cast<char*>(staged) + (reinterpret_cast<char*>(w.tile_start) - static_cast<char*>(w.descs)));
+  int64_t t = 0, off = 0;
+  int lg = 4;  // the smallest alignment class (OR of addresses and row pitches) over the groups that are read
+  for (int64_t i = 0; i < G; ++i) {
+    const pyg_hip_group& g = host_groups[i];
+    ht[i] = (int32_t)t;
+    t += (g.rows + kTile - 1) / kTile * dw_describe(hd[i], static_cast<const char*>(g.input), static_cast<const char*>(g.other),
+                                                    g.rows, g.k, g.m, elt, off, r.K, r.MC);
+    PYG_HIP_REQUIRE(t < (1LL << 31), "grouped_matmul_dw: too many tiles");
+    if (g.rows > 0 && g.k > 0 && g.m > 0)
+      lg = std::min(lg, gen_log2_align((uint64_t)g.input | (uint64_t)(g.k * elt) | (uint64_t)g.other | (uint64_t)(g.m * elt)));
+    off += (int64_t)g.k * g.m;
+  }
+  ht[G] = (int32_t)t;
+  PYG_HIP_CHECK(hipMemcpyAsync(w.descs, staged, w.plan_bytes, hipMemcpyHostToDevice, stream));
+  rc = pinned_stage().commit(stream);
+  if (rc != PYG_HIP_OK) return rc;
+  if (r.family != DwFamily::kGen) return run_dw_route(r, dtype, w, G, host_groups[0].m, t + 1, out_pool, lg, stream);
+  if (off == 0) return PYG_HIP_OK;
+  if (t == 0) {  // no rows anywhere: the result is all zeros
+    PYG_HIP_CHECK(hipMemsetAsync(out_pool, 0, (size_t)elt * (size_t)off, stream));
+    return PYG_HIP_OK;
+  }
+  return run_dw_route(r, dtype, w, G, 0, t, out_pool, lg, stream);
+}
 
 }  // namespace
 }  // namespace pyg_hip
 
 using namespace pyg_hip;
-
-namespace {
-// launches of the shape-specialised / the general-shape weight-gradient kernels since the library was loaded (tests
-// assert that a backward pass ran a device kernel and not the caller's fallback formula; the backward runs on an
-// autograd thread, so a thread-local "last variant" would not be visible to the test)
-std::atomic<int64_t> g_dw_fast{0}, g_dw_gen{0};
-}  // namespace
 
 extern "C" {
 
@@ -760,17 +935,20 @@ void pyg_hip_matmul_dw_counters(int64_t* specialised, int64_t* general) {
   if (general) *general = g_dw_gen.load();
 }
 
+const char* pyg_hip_matmul_dw_route(int dtype, int64_t K, int64_t M, int uniform, unsigned misalign) {
+  if (K < 0 || M < 0) return "invalid";
+  return dw_route_name(dtype, choose_dw_route(dtype, K, M, uniform != 0, misalign));
+}
+
 size_t pyg_hip_segment_matmul_dw_workspace_size(int64_t B, int64_t K, int64_t M) {
-  B = B < 0 ? 0 : B, K = K < 0 ? 0 : K, M = M < 0 ? 0 : M;
-  return std::max(dw_ws_bytes(B, K, M), dw_gen_workspace_bytes(B));
+  return dw_workspace_bytes(std::max<int64_t>(B, 0), std::max<int64_t>(K, 0), std::max<int64_t>(M, 0), true);
 }
 
 size_t pyg_hip_grouped_matmul_dw_workspace_size(const pyg_hip_group* groups, int64_t G) {
-  if (G <= 0 || groups == nullptr) return dw_gen_workspace_bytes(0);
+  if (G <= 0 || groups == nullptr) return dw_workspace_bytes(0, 0, 0, false);
   bool uniform = true;
   for (int64_t i = 0; i < G; ++i) uniform = uniform && groups[i].k == groups[0].k && groups[i].m == groups[0].m;
-  const size_t gen = dw_gen_workspace_bytes(G);
-  return uniform ? std::max(gen, dw_ws_bytes(G, std::max(groups[0].k, 0), std::max(groups[0].m, 0))) : gen;
+  return dw_workspace_bytes(G, std::max(groups[0].k, 0), std::max(groups[0].m, 0), uniform);
 }
 
 int pyg_hip_segment_matmul_dw(int dtype, const void* input, const int64_t* ptr, int ptr_on_device, const void* grad_out,
@@ -780,45 +958,17 @@ int pyg_hip_segment_matmul_dw(int dtype, const void* input, const int64_t* ptr, 
   PYG_HIP_REQUIRE(N >= 0 && K >= 0 && M >= 0 && B >= 0, "segment_matmul_dw: negative size");
   if (B * K * M == 0) return PYG_HIP_OK;
   PYG_HIP_REQUIRE(ptr && grad_other && (N == 0 || (input && grad_out)), "segment_matmul_dw: NULL tensor");
-  if (dtype != PYG_BF16 && dtype != PYG_F16 && dtype != PYG_F32)
+  if (!dw_dtype_ok(dtype))
     return fail(PYG_HIP_ERR_UNSUPPORTED, "segment_matmul_dw: float32 / bfloat16 / float16 only (dtype %d)", dtype);
   const size_t need = pyg_hip_segment_matmul_dw_workspace_size(B, K, M);
   if (workspace == nullptr || workspace_bytes < need)
     return fail(PYG_HIP_ERR_WORKSPACE, "segment_matmul_dw: workspace of %zu bytes needed, got %zu", need, workspace_bytes);
-  if (!dw_fast_shape(K, M) || ((uintptr_t)input | (uintptr_t)grad_out) % 16 != 0) {
-    const int rc = dw_gen_segment(dtype, input, ptr, ptr_on_device, grad_out, grad_other, N, K, M, B, workspace, stream);
-    if (rc == PYG_HIP_OK) ++g_dw_gen;
-    return rc;
-  }
-  ++g_dw_fast;
-  char* w = static_cast<char*>(workspace);
-  int64_t* ptr_dev = reinterpret_cast<int64_t*>(w);
-  w += align_up(sizeof(int64_t) * (size_t)(B + 1), 256);
-  DwGroup* groups = reinterpret_cast<DwGroup*>(w);
-  w += dw_groups_bytes(B);
-  int32_t* tile_start = reinterpret_cast<int32_t*>(w);
-  w += dw_tiles_bytes(B);
-  float* slabs = reinterpret_cast<float*>(w);
-  const int64_t* dptr = ptr;
-  if (!ptr_on_device) {
-    void* staged = nullptr;
-    int rc = pinned_stage().acquire(sizeof(int64_t) * (size_t)(B + 1), &staged);
-    if (rc != PYG_HIP_OK) return rc;
-    ::memcpy(staged, ptr, sizeof(int64_t) * (size_t)(B + 1));
-    PYG_HIP_CHECK(hipMemcpyAsync(ptr_dev, staged, sizeof(int64_t) * (size_t)(B + 1), hipMemcpyHostToDevice, stream));
-    rc = pinned_stage().commit(stream);
-    if (rc != PYG_HIP_OK) return rc;
-    dptr = ptr_dev;
-  }
-  // descriptors address the tensors in 2-byte units: an fp32 row is 2 K of them
-  const int64_t u = dtype == PYG_F32 ? 2 : 1;
-  hipLaunchKernelGGL(dw_plan_kernel, dim3(1), dim3(256), 0, stream, dptr, B, static_cast<const uint16_t*>(input),
-                     static_cast<const uint16_t*>(grad_out), K * u, M * u, groups, tile_start);
-  PYG_HIP_CHECK(hipGetLastError());
-  const int64_t tiles_upper = (N + kTile - 1) / kTile + B;
-  return dtype == PYG_F32    ? run_dw_f32(groups, tile_start, B, K, M, tiles_upper, slabs, grad_other, stream)
-         : dtype == PYG_BF16 ? run_dw<bf16_tag>(groups, tile_start, B, K, M, tiles_upper, slabs, grad_other, stream)
-                             : run_dw<f16_tag>(groups, tile_start, B, K, M, tiles_upper, slabs, grad_other, stream);
+  const unsigned misalign = dw_misalign((uintptr_t)input | (uintptr_t)grad_out, grad_other, dw_elt(dtype));
+  const DwRoute r = choose_dw_route(dtype, K, M, true, misalign);
+  if (int rc = dw_route_check("segment_matmul_dw", r, K, M)) return rc;
+  return dw_count(r, r.family == DwFamily::kGen
+                         ? dw_segment<DwGenGroup>(r, dtype, input, ptr, ptr_on_device, grad_out, grad_other, N, K, M, B, workspace, stream)
+                         : dw_segment<DwGroup>(r, dtype, input, ptr, ptr_on_device, grad_out, grad_other, N, K, M, B, workspace, stream));
 }
 
 int pyg_hip_grouped_matmul_dw(int dtype, const pyg_hip_group* host_groups, int64_t G, void* out_pool, void* workspace,
@@ -827,56 +977,32 @@ int pyg_hip_grouped_matmul_dw(int dtype, const pyg_hip_group* host_groups, int64
   PYG_HIP_REQUIRE(G >= 0 && G < (1LL << 31), "grouped_matmul_dw: bad group count");
   if (G == 0) return PYG_HIP_OK;
   PYG_HIP_REQUIRE(host_groups && out_pool, "grouped_matmul_dw: NULL argument");
-  if (dtype != PYG_BF16 && dtype != PYG_F16 && dtype != PYG_F32)
+  if (!dw_dtype_ok(dtype))
     return fail(PYG_HIP_ERR_UNSUPPORTED, "grouped_matmul_dw: float32 / bfloat16 / float16 only (dtype %d)", dtype);
   const int64_t K = host_groups[0].k, M = host_groups[0].m;
-  int64_t tiles = 0;
-  bool fast = dw_fast_shape(K, M);
+  bool uniform = true;
+  uintptr_t operands = 0;
   for (int64_t i = 0; i < G; ++i) {
     const pyg_hip_group& g = host_groups[i];
     PYG_HIP_REQUIRE(g.rows >= 0 && g.k >= 0 && g.m >= 0, "grouped_matmul_dw: negative size in group %lld", (long long)i);
     PYG_HIP_REQUIRE(g.rows == 0 || g.k == 0 || g.m == 0 || (g.input && g.other), "grouped_matmul_dw: NULL tensor in group %lld",
                     (long long)i);
-    if (g.k != K || g.m != M || ((uintptr_t)g.input | (uintptr_t)g.other) % 16 != 0) fast = false;
-    tiles += (g.rows + kTile - 1) / kTile;
+    uniform = uniform && g.k == K && g.m == M;
+    operands |= (uintptr_t)g.input | (uintptr_t)g.other;
   }
   const size_t need = pyg_hip_grouped_matmul_dw_workspace_size(host_groups, G);
   if (workspace == nullptr || workspace_bytes < need)
     return fail(PYG_HIP_ERR_WORKSPACE, "grouped_matmul_dw: workspace of %zu bytes needed, got %zu", need, workspace_bytes);
-  // per-group shapes, shapes without a specialised kernel, element-aligned views: the general-shape kernel
-  if (!fast) {
-    const int rc = dw_gen_grouped(dtype, host_groups, G, out_pool, workspace, stream);
-    if (rc == PYG_HIP_OK) ++g_dw_gen;
-    return rc;
-  }
-  ++g_dw_fast;
-  char* w = static_cast<char*>(workspace) + align_up(sizeof(int64_t) * (size_t)(G + 1), 256);
-  DwGroup* groups = reinterpret_cast<DwGroup*>(w);
-  w += dw_groups_bytes(G);
-  int32_t* tile_start = reinterpret_cast<int32_t*>(w);
-  w += dw_tiles_bytes(G);
-  float* slabs = reinterpret_cast<float*>(w);
-  // host-side plan (G is small): descriptors + tile prefix in one pinned H2D copy
-  void* staged = nullptr;
-  int rc = pinned_stage().acquire(dw_groups_bytes(G) + dw_tiles_bytes(G), &staged);
-  if (rc != PYG_HIP_OK) return rc;
-  DwGroup* hg = static_cast<DwGroup*>(staged);
-  int32_t* ht = reinterpret_cast<int32_t*>(static_cast<char*>(staged) + dw_groups_bytes(G));
-  int64_t t = 0;
+  // per-group shapes, shapes without a specialised kernel, element-aligned views: the general-shape kernel, whose limits
+  // then hold for every group
+  const unsigned misalign = dw_misalign(operands, out_pool, dw_elt(dtype));
+  const DwRoute r = choose_dw_route(dtype, K, M, uniform, misalign);
   for (int64_t i = 0; i < G; ++i) {
-    hg[i].x = static_cast<const uint16_t*>(host_groups[i].input);
-    hg[i].dy = static_cast<const uint16_t*>(host_groups[i].other);
-    hg[i].rows = host_groups[i].rows;
-    ht[i] = (int32_t)t;
-    t += (host_groups[i].rows + kTile - 1) / kTile;
+    const int64_t k = host_groups[i].k, m = host_groups[i].m;
+    if (int rc = dw_route_check("grouped_matmul_dw", choose_dw_route(dtype, k, m, uniform, misalign), k, m)) return rc;
   }
-  ht[G] = (int32_t)t;
-  PYG_HIP_CHECK(hipMemcpyAsync(groups, staged, dw_groups_bytes(G) + dw_tiles_bytes(G), hipMemcpyHostToDevice, stream));
-  rc = pinned_stage().commit(stream);
-  if (rc != PYG_HIP_OK) return rc;
-  return dtype == PYG_F32    ? run_dw_f32(groups, tile_start, G, K, M, tiles + 1, slabs, out_pool, stream)
-         : dtype == PYG_BF16 ? run_dw<bf16_tag>(groups, tile_start, G, K, M, tiles + 1, slabs, out_pool, stream)
-                             : run_dw<f16_tag>(groups, tile_start, G, K, M, tiles + 1, slabs, out_pool, stream);
+  return dw_count(r, r.family == DwFamily::kGen ? dw_grouped<DwGenGroup>(r, dtype, host_groups, G, out_pool, workspace, stream)
+                                                : dw_grouped<DwGroup>(r, dtype, host_groups, G, out_pool, workspace, stream));
 }
 
 }  // extern "C"

@@ -27,9 +27,6 @@
 #include "matmul_dw_out.h"
 
 #include <stdint.h>
-#include <string.h>
-
-#include <algorithm>
 
 namespace pyg_hip {
 namespace {
@@ -39,17 +36,6 @@ typedef short v8i16 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kTile = 128;  // rows per workgroup tile (4 waves x 32)
-
-struct DwGenGroup {  // 48 bytes
-  const char* x;     // [rows, k] row-major
-  const char* dy;    // [rows, m] row-major
-  int64_t rows;
-  int64_t acc_off;   // first element of this group's [k, m] block in the fp32 image (and in the output pool)
-  int32_t k, m;
-  int16_t lx, ly;    // log2 of the vector bytes the X / dY rows may be fetched with (1 ... 4)
-  int16_t nkb, nmb;  // blocks along k and m
-};
-static_assert(sizeof(DwGenGroup) == 48, "DwGenGroup layout");
 
 template <typename T>
 struct GenCfg;
@@ -318,53 +304,6 @@ __global__ __launch_bounds__(256, 1) void dw_gen_kernel(const DwGenGroup* __rest
   flush();
 }
 
-// segment form: descriptors + tile prefix from `ptr` (uniform K, M; one thread per run of relations)
-__global__ void dw_gen_plan_kernel(const int64_t* __restrict__ ptr, int64_t B, const char* X, const char* dY, int64_t K,
-                                   int64_t M, int elt, int kb_size, int mb_size, DwGenGroup* __restrict__ groups,
-                                   int32_t* __restrict__ tile_start) {
-  __shared__ int64_t part[256];
-  const int tid = threadIdx.x;
-  const int64_t per = (B + 255) / 256;
-  const int64_t beg = min((int64_t)tid * per, B), end = min(beg + per, B);
-  const int nkb = (int)((K + kb_size - 1) / kb_size), nmb = (int)((M + mb_size - 1) / mb_size);
-  int64_t t = 0;
-  for (int64_t b = beg; b < end; ++b) {
-    const int64_t r = ptr[b + 1] - ptr[b];
-    t += r > 0 ? (r + kTile - 1) / kTile * nkb * nmb : 0;
-  }
-  part[tid] = t;
-  __syncthreads();
-  if (tid == 0) {
-    int64_t acc = 0;
-    for (int i = 0; i < 256; ++i) {
-      const int64_t v = part[i];
-      part[i] = acc;
-      acc += v;
-    }
-    tile_start[B] = (int32_t)acc;
-  }
-  __syncthreads();
-  t = part[tid];
-  for (int64_t b = beg; b < end; ++b) {
-    tile_start[b] = (int32_t)t;
-    const int64_t p0 = ptr[b];
-    const int64_t r = ptr[b + 1] - p0;
-    DwGenGroup d;
-    d.x = X + p0 * K * elt;
-    d.dy = dY + p0 * M * elt;
-    d.rows = r > 0 ? r : 0;
-    d.acc_off = b * K * M;
-    d.k = (int32_t)K;
-    d.m = (int32_t)M;
-    d.lx = (int16_t)min(gen_log2_align((uint64_t)d.x), gen_log2_align((uint64_t)(K * elt)));
-    d.ly = (int16_t)min(gen_log2_align((uint64_t)d.dy), gen_log2_align((uint64_t)(M * elt)));
-    d.nkb = (int16_t)nkb;
-    d.nmb = (int16_t)nmb;
-    groups[b] = d;
-    t += r > 0 ? (r + kTile - 1) / kTile * nkb * nmb : 0;
-  }
-}
-
 // The launch behind dw_gen_kernel (see seg_dw_fixup_kernel in matmul_dw.hip): workgroups [0, fix_blocks) add the slabs
 // of the (group, block) units that are split over main workgroups, in workgroup order; the ones behind them write the
 // zeros of groups without rows.
@@ -407,16 +346,16 @@ __global__ __launch_bounds__(256) void dw_gen_fixup_kernel(const DwGenGroup* __r
 }
 
 template <typename T, int LG>
-int launch_gen_lg(const DwGenGroup* groups, const int32_t* tile_start, int B, int64_t tiles_upper, float* slabs, void* out_,
+int launch_gen_lg(const DwGenGroup* groups, const int32_t* tile_start, int B, int64_t gx, float* slabs, void* out_,
                   hipStream_t stream) {
   constexpr int ELT = Elem<T>::kSize;
   constexpr int lds = 4 * 32 * (gen_pitch<ELT>(32 * GenCfg<T>::IB) + gen_pitch<ELT>(32 * GenCfg<T>::JB));
   static_assert(lds <= 160 * 1024, "dw_gen_kernel: LDS");
   static_assert(lds >= GenCfg<T>::IB * GenCfg<T>::JB * 4096, "the combine area must fit the row images");
+  static_assert(32 * GenCfg<T>::IB == kDwGenKB && 32 * GenCfg<T>::JB == dw_gen_mb(ELT), "the block the plan and the slabs are cut for");
   T* out = static_cast<T*>(out_);
   const void* kern = reinterpret_cast<const void*>(&dw_gen_kernel<T, LG>);
   if (int rc_ = ensure_dynamic_lds(kern, lds)) return rc_;
-  const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(tiles_upper, device_info().num_cus));
   hipLaunchKernelGGL((dw_gen_kernel<T, LG>), dim3((unsigned)gx), dim3(256), lds, stream, groups, tile_start, B, slabs, out);
   PYG_HIP_CHECK(hipGetLastError());
   const int64_t fix_blocks = gx * GenCfg<T>::IB * GenCfg<T>::JB;
@@ -426,132 +365,26 @@ int launch_gen_lg(const DwGenGroup* groups, const int32_t* tile_start, int B, in
   return PYG_HIP_OK;
 }
 
-// `lg`: alignment class of the launch = the smallest over its groups' operands (log2 of the vector bytes)
+// one of four instantiations per type: the alignment class of the launch (LG = 1 exists for the 16-bit types only)
 template <typename T>
-int launch_gen(const DwGenGroup* groups, const int32_t* tile_start, int B, int64_t tiles_upper, float* slabs, void* out, int lg,
+int launch_gen(const DwGenGroup* groups, const int32_t* tile_start, int B, int64_t gx, float* slabs, void* out, int lg,
                hipStream_t stream) {
-  if (lg >= 4) return launch_gen_lg<T, 4>(groups, tile_start, B, tiles_upper, slabs, out, stream);
-  if (lg == 3) return launch_gen_lg<T, 3>(groups, tile_start, B, tiles_upper, slabs, out, stream);
+  if (lg >= 4) return launch_gen_lg<T, 4>(groups, tile_start, B, gx, slabs, out, stream);
+  if (lg == 3) return launch_gen_lg<T, 3>(groups, tile_start, B, gx, slabs, out, stream);
   if constexpr (Elem<T>::kSize == 2) {
-    if (lg <= 1) return launch_gen_lg<T, 1>(groups, tile_start, B, tiles_upper, slabs, out, stream);
+    if (lg <= 1) return launch_gen_lg<T, 1>(groups, tile_start, B, gx, slabs, out, stream);
   }
-  return launch_gen_lg<T, 2>(groups, tile_start, B, tiles_upper, slabs, out, stream);
+  return launch_gen_lg<T, 2>(groups, tile_start, B, gx, slabs, out, stream);
 }
-
-inline int gen_kb(int dtype) { return dtype == PYG_F32 ? 32 * GenCfg<float>::IB : 32 * GenCfg<bf16_t>::IB; }
-inline int gen_mb(int dtype) { return dtype == PYG_F32 ? 32 * GenCfg<float>::JB : 32 * GenCfg<bf16_t>::JB; }
-
-int run_gen(int dtype, const DwGenGroup* groups, const int32_t* tile_start, int64_t B, int64_t tiles_upper, float* slabs,
-            void* out, int lg, hipStream_t stream) {
-  return dtype == PYG_F32    ? launch_gen<float>(groups, tile_start, (int)B, tiles_upper, slabs, out, lg, stream)
-         : dtype == PYG_BF16 ? launch_gen<bf16_t>(groups, tile_start, (int)B, tiles_upper, slabs, out, lg, stream)
-                             : launch_gen<f16_t>(groups, tile_start, (int)B, tiles_upper, slabs, out, lg, stream);
-}
-
-inline size_t gen_groups_bytes(int64_t B) { return align_up(sizeof(DwGenGroup) * (size_t)(B > 0 ? B : 1), 256); }
-inline size_t gen_tiles_bytes(int64_t B) { return align_up(sizeof(int32_t) * (size_t)(B + 1), 256); }
 
 }  // namespace
 
-size_t dw_gen_workspace_bytes(int64_t B) {
-  // two fp32 slabs of one 128 x 128 block per main workgroup (the 16-bit configuration is the larger one)
-  const size_t slabs = (size_t)device_info().num_cus * 2 * (size_t)(GenCfg<bf16_t>::IB * GenCfg<bf16_t>::JB) * kDwBlockFloats *
-                       sizeof(float);
-  return align_up(sizeof(int64_t) * (size_t)(B + 1), 256) + gen_groups_bytes(B) + gen_tiles_bytes(B) + slabs;
-}
-
-int dw_gen_segment(int dtype, const void* input, const int64_t* ptr, int ptr_on_device, const void* grad_out,
-                   void* grad_other, int64_t N, int64_t K, int64_t M, int64_t B, void* workspace, hipStream_t stream) {
-  const int elt = dtype == PYG_F32 ? 4 : 2;
-  PYG_HIP_REQUIRE(((uintptr_t)input | (uintptr_t)grad_out | (uintptr_t)grad_other) % elt == 0,
-                  "segment_matmul_dw: tensors must be element-aligned");
-  if (K >= (1LL << 21) || M >= (1LL << 21) || K * M >= (1LL << 28))
-    return fail(PYG_HIP_ERR_UNSUPPORTED, "segment_matmul_dw: K x M = %lld x %lld is beyond the kernel's 32-bit offsets", (long long)K,
-                (long long)M);
-  const int kb = gen_kb(dtype), mb = gen_mb(dtype);
-  const int64_t blocks = ((K + kb - 1) / kb) * ((M + mb - 1) / mb);
-  const int64_t tiles_upper = ((N + kTile - 1) / kTile + B) * blocks;
-  PYG_HIP_REQUIRE(tiles_upper < (1LL << 31), "segment_matmul_dw: too many tiles");
-  char* w = static_cast<char*>(workspace);
-  int64_t* ptr_dev = reinterpret_cast<int64_t*>(w);
-  w += align_up(sizeof(int64_t) * (size_t)(B + 1), 256);
-  DwGenGroup* groups = reinterpret_cast<DwGenGroup*>(w);
-  w += gen_groups_bytes(B);
-  int32_t* tile_start = reinterpret_cast<int32_t*>(w);
-  w += gen_tiles_bytes(B);
-  float* slabs = reinterpret_cast<float*>(w);
-  const int64_t* dptr = ptr;
-  if (!ptr_on_device) {
-    void* staged = nullptr;
-    int rc = pinned_stage().acquire(sizeof(int64_t) * (size_t)(B + 1), &staged);
-    if (rc != PYG_HIP_OK) return rc;
-    ::memcpy(staged, ptr, sizeof(int64_t) * (size_t)(B + 1));
-    PYG_HIP_CHECK(hipMemcpyAsync(ptr_dev, staged, sizeof(int64_t) * (size_t)(B + 1), hipMemcpyHostToDevice, stream));
-    rc = pinned_stage().commit(stream);
-    if (rc != PYG_HIP_OK) return rc;
-    dptr = ptr_dev;
-  }
-  hipLaunchKernelGGL(dw_gen_plan_kernel, dim3(1), dim3(256), 0, stream, dptr, B, static_cast<const char*>(input),
-                     static_cast<const char*>(grad_out), K, M, elt, kb, mb, groups, tile_start);
-  PYG_HIP_CHECK(hipGetLastError());
-  // a relation starts ptr[b] rows into the tensors: its alignment is at least that of the base and the row pitch
-  const int lg = std::min(std::min(gen_log2_align((uint64_t)input), gen_log2_align((uint64_t)(K * elt))),
-                          std::min(gen_log2_align((uint64_t)grad_out), gen_log2_align((uint64_t)(M * elt))));
-  return run_gen(dtype, groups, tile_start, B, tiles_upper, slabs, grad_other, lg, stream);
-}
-
-int dw_gen_grouped(int dtype, const pyg_hip_group* host_groups, int64_t G, void* out_pool, void* workspace,
-                   hipStream_t stream) {
-  const int elt = dtype == PYG_F32 ? 4 : 2;
-  const int kb = gen_kb(dtype), mb = gen_mb(dtype);
-  char* w = static_cast<char*>(workspace) + align_up(sizeof(int64_t) * (size_t)(G + 1), 256);
-  DwGenGroup* groups = reinterpret_cast<DwGenGroup*>(w);
-  w += gen_groups_bytes(G);
-  int32_t* tile_start = reinterpret_cast<int32_t*>(w);
-  w += gen_tiles_bytes(G);
-  float* slabs = reinterpret_cast<float*>(w);
-  void* staged = nullptr;
-  int rc = pinned_stage().acquire(gen_groups_bytes(G) + gen_tiles_bytes(G), &staged);
-  if (rc != PYG_HIP_OK) return rc;
-  DwGenGroup* hg = static_cast<DwGenGroup*>(staged);
-  int32_t* ht = reinterpret_cast<int32_t*>(static_cast<char*>(staged) + gen_groups_bytes(G));
-  int64_t t = 0, off = 0;
-  int lg = 4;
-  for (int64_t i = 0; i < G; ++i) {
-    const pyg_hip_group& g = host_groups[i];
-    if (g.k >= (1 << 21) || g.m >= (1 << 21) || (int64_t)g.k * g.m >= (1LL << 28))
-      return fail(PYG_HIP_ERR_UNSUPPORTED, "grouped_matmul_dw: K x M = %d x %d is beyond the kernel's 32-bit offsets", g.k, g.m);
-    PYG_HIP_REQUIRE(((uintptr_t)g.input | (uintptr_t)g.other) % elt == 0, "grouped_matmul_dw: operands must be element-aligned");
-    DwGenGroup d;
-    d.x = static_cast<const char*>(g.input);
-    d.dy = static_cast<const char*>(g.other);
-    d.rows = g.rows;
-    d.acc_off = off;
-    d.k = g.k;
-    d.m = g.m;
-    d.lx = (int16_t)std::min(gen_log2_align((uint64_t)d.x), gen_log2_align((uint64_t)((int64_t)g.k * elt)));
-    d.ly = (int16_t)std::min(gen_log2_align((uint64_t)d.dy), gen_log2_align((uint64_t)((int64_t)g.m * elt)));
-    d.nkb = (int16_t)((g.k + kb - 1) / kb);
-    d.nmb = (int16_t)((g.m + mb - 1) / mb);
-    PYG_HIP_REQUIRE(d.nkb >= 0 && d.nmb >= 0 && (g.k + kb - 1) / kb < 32768 && (g.m + mb - 1) / mb < 32768,
-                    "grouped_matmul_dw: K / M too large");
-    if (g.rows > 0 && g.k > 0 && g.m > 0) lg = std::min(lg, (int)std::min(d.lx, d.ly));
-    hg[i] = d;
-    ht[i] = (int32_t)t;
-    t += (g.rows + kTile - 1) / kTile * (int64_t)d.nkb * d.nmb;
-    PYG_HIP_REQUIRE(t < (1LL << 31), "grouped_matmul_dw: too many tiles");
-    off += (int64_t)g.k * g.m;
-  }
-  ht[G] = (int32_t)t;
-  PYG_HIP_CHECK(hipMemcpyAsync(groups, staged, gen_groups_bytes(G) + gen_tiles_bytes(G), hipMemcpyHostToDevice, stream));
-  rc = pinned_stage().commit(stream);
-  if (rc != PYG_HIP_OK) return rc;
-  if (off == 0) return PYG_HIP_OK;
-  if (t == 0) {  // no rows anywhere: the result is all zeros
-    PYG_HIP_CHECK(hipMemsetAsync(out_pool, 0, (size_t)elt * (size_t)off, stream));
-    return PYG_HIP_OK;
-  }
-  return run_gen(dtype, groups, tile_start, G, t, slabs, out_pool, lg, stream);
+int launch_dw_gen(int dtype, const void* descs, const int32_t* tile_start, int B, int64_t gx, float* slabs, void* out, int lg,
+                  hipStream_t stream) {
+  const DwGenGroup* groups = static_cast<const DwGenGroup*>(descs);
+  return dtype == PYG_F32    ? launch_gen<float>(groups, tile_start, B, gx, slabs, out, lg, stream)
+         : dtype == PYG_BF16 ? launch_gen<bf16_t>(groups, tile_start, B, gx, slabs, out, lg, stream)
+                             : launch_gen<f16_t>(groups, tile_start, B, gx, slabs, out, lg, stream);
 }
 
 }  // namespace pyg_hip

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests._guard import assert_no_poison, big_value, guarded, guarded_copy
+from tests._guard import assert_no_poison, big_value, guarded, guarded_copy, poisoned
 from tests._paths import CSR_CASES, _csr_shape, _lens, csr_path
 
 pytestmark = pytest.mark.gpu
@@ -62,6 +62,7 @@ def lib():
     _sig(L, 'pyg_hip_segment_matmul_dw', I32, [I32, P, P, I32, P, P, I64, I64, I64, I64, P, SZ, P])
     _sig(L, 'pyg_hip_grouped_matmul_dw', I32, [I32, P, I64, P, P, SZ, P])
     _sig(L, 'pyg_hip_matmul_dw_counters', None, [c.POINTER(I64), c.POINTER(I64)])
+    _sig(L, 'pyg_hip_matmul_dw_route', c.c_char_p, [I32, I64, I64, I32, c.c_uint])
     _sig(L, 'pyg_hip_scatter_workspace_size', SZ, [I64, I64, I64])
     _sig(L, 'pyg_hip_scatter', I32, [I32, I32, P, P, I64, I64, I64, P, P, P, I64, I64, I64, I64, I32, P, SZ, P])
     _sig(L, 'pyg_hip_fill_reduce_identity', I32, [I32, I32, P, I64, P])
@@ -260,23 +261,40 @@ def _dw_counters(lib):
     return a.value, b.value
 
 
+def _dw_route(lib, dtype, K, M, uniform, operands, out):
+    """pyg_hip_matmul_dw_route for a call with the X / dY addresses `operands` and the output address `out`."""
+    misalign = 0
+    for p in operands:
+        misalign |= p & 15
+    misalign |= out & (torch.empty((), dtype=dtype).element_size() - 1)
+    return lib.pyg_hip_matmul_dw_route(CODE[dtype], K, M, uniform, misalign).decode()
+
+
 @pytest.mark.parametrize('dtype,K,M,specialised', [(torch.float32, 128, 128, True), (torch.bfloat16, 64, 64, True),
                                                    (torch.bfloat16, 256, 128, True), (torch.bfloat16, 47, 9, False),
                                                    (torch.float16, 100, 129, False), (torch.float32, 1, 7, False),
-                                                   (torch.float32, 129, 100, False)])
+                                                   (torch.float32, 129, 100, False), (torch.bfloat16, 128, 128, False)])
 def test_segment_matmul_dw(lib, dtype, K, M, specialised):
+    # A row that names the general kernel for a shape with a specialised one (the last) gets there through its X: it starts
+    # one element into its buffer -- the smallest input on which the 16-byte rule of the specialised kernels can go wrong.
+    x_off = int(not specialised and lib.pyg_hip_matmul_dw_route(CODE[dtype], K, M, 1, 0) != b'gen')
+    assert x_off == int((dtype, K, M) == (torch.bfloat16, 128, 128))
     rng = np.random.default_rng(K + 3 * M)
     ptr_host = np.concatenate([[0], np.cumsum(SEGMENTS)]).astype(np.int64)
     N, B = int(ptr_host[-1]), len(SEGMENTS)
     x, dy = rand(rng, (N, K), dtype), rand(rng, (N, M), dtype)
     g = Guards()
-    xd, dyd = g.inp(x), g.inp(dy)
+    # (the elements in front of a shifted X are NaN: a kernel that rounds the address down reads them)
+    x_ptr = g.inp(torch.cat([torch.full((x_off,), float('nan'), dtype=dtype), x.flatten()])).data_ptr() + x_off * x.element_size()
+    dyd = g.inp(dy)
     pd = g.inp(torch.from_numpy(ptr_host), fill=N)
     out = g.out((B, K, M), dtype)       # every [K, M] block is written, also those of empty segments
     ws_bytes = lib.pyg_hip_segment_matmul_dw_workspace_size(B, K, M)
     ws = g.ws(ws_bytes)
+    route = _dw_route(lib, dtype, K, M, 1, [x_ptr, dyd.data_ptr()], out.data_ptr())
+    assert specialised == (route != 'gen'), route
     before = _dw_counters(lib)
-    ok(lib, lib.pyg_hip_segment_matmul_dw(CODE[dtype], xd.data_ptr(), pd.data_ptr(), 1, dyd.data_ptr(), out.data_ptr(), N, K, M,
+    ok(lib, lib.pyg_hip_segment_matmul_dw(CODE[dtype], x_ptr, pd.data_ptr(), 1, dyd.data_ptr(), out.data_ptr(), N, K, M,
                                           B, ptr(ws), ws_bytes, stream()))
     torch.cuda.synchronize()
     after = _dw_counters(lib)
@@ -289,25 +307,60 @@ def test_segment_matmul_dw(lib, dtype, K, M, specialised):
     close(out, want, max(rtol, 1e-5), atol * 4 if dtype != torch.float32 else 1e-4, what='dw')
 
 
+@pytest.mark.parametrize('K,M', [(64, 64), (47, 9)])          # a specialised and a general route
+@pytest.mark.parametrize('bad_ptr', [[0, 5, 3], [0, 3, 9]])   # decreasing; last entry beyond N = 8
+def test_segment_matmul_dw_rejects_a_bad_host_ptr(lib, K, M, bad_ptr):
+    """A host `ptr` is checked before anything is launched: PYG_HIP_ERR_INVALID, no counter moves, nothing is written."""
+    dtype, N, B = torch.bfloat16, 8, 2
+    rng = np.random.default_rng(5)
+    g = Guards()
+    xd, dyd = g.inp(rand(rng, (N, K), dtype)), g.inp(rand(rng, (N, M), dtype))
+    out = g.out((B, K, M), dtype)
+    ws_bytes = lib.pyg_hip_segment_matmul_dw_workspace_size(B, K, M)
+    ws = g.ws(ws_bytes)
+    ptr_host = np.asarray(bad_ptr, dtype=np.int64)
+    before = _dw_counters(lib)
+    rc = lib.pyg_hip_segment_matmul_dw(CODE[dtype], xd.data_ptr(), ptr_host.ctypes.data, 0, dyd.data_ptr(), out.data_ptr(), N, K,
+                                       M, B, ptr(ws), ws_bytes, stream())
+    torch.cuda.synchronize()
+    assert rc == -1, rc                                       # PYG_HIP_ERR_INVALID
+    assert b"'ptr' must be non-decreasing" in lib.pyg_hip_last_error()
+    assert _dw_counters(lib) == before
+    g.check()
+    assert bool(poisoned(out).all()) and bool(poisoned(ws).all())
+
+
+# ragged per-group shapes (the general kernel); a uniform, 16-byte aligned list whose 300-row group spans several tiles
+DW_GROUPS = [([(33, 47, 9), (0, 7, 100), (129, 129, 1), (1, 64, 64), (127, 9, 7)], 'gen'),
+             ([(1, 64, 64), (129, 64, 64), (300, 64, 64)], 'seg_{}_k64_mc64')]   # rows, k_i, m_i
+
+
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32])
 def test_grouped_matmul_dw(lib, dtype):
     rng = np.random.default_rng(11)
-    shapes = [(33, 47, 9), (0, 7, 100), (129, 129, 1), (1, 64, 64), (127, 9, 7)]   # rows, k_i, m_i
-    g = Guards()
-    descs, wants = (Group * len(shapes))(), []
-    for i, (rows, k, m) in enumerate(shapes):
-        x, dy = rand(rng, (rows, k), dtype), rand(rng, (rows, m), dtype)
-        descs[i] = Group(g.inp(x).data_ptr(), g.inp(dy).data_ptr(), None, rows, k, m, 0, 0)
-        wants.append((x.double().t() @ dy.double()).flatten())
-    pool = g.out(sum(k * m for _, k, m in shapes), dtype)
-    ws_bytes = lib.pyg_hip_grouped_matmul_dw_workspace_size(c.addressof(descs), len(shapes))
-    ws = g.ws(ws_bytes)
-    ok(lib, lib.pyg_hip_grouped_matmul_dw(CODE[dtype], c.addressof(descs), len(shapes), pool.data_ptr(), ptr(ws), ws_bytes,
-                                          stream()))
-    torch.cuda.synchronize()
-    g.check()
-    assert_no_poison(pool, 'grouped_matmul_dw pool')
-    close(pool, torch.cat(wants), max(TOL[dtype][0], 1e-5), 1e-4 if dtype == torch.float32 else 0.12, what='grouped dw')
+    for shapes, route in DW_GROUPS:
+        g = Guards()
+        descs, wants, operands = (Group * len(shapes))(), [], []
+        for i, (rows, k, m) in enumerate(shapes):
+            x, dy = rand(rng, (rows, k), dtype), rand(rng, (rows, m), dtype)
+            operands += [g.inp(x).data_ptr(), g.inp(dy).data_ptr()]
+            descs[i] = Group(operands[-2], operands[-1], None, rows, k, m, 0, 0)
+            wants.append((x.double().t() @ dy.double()).flatten())
+        pool = g.out(sum(k * m for _, k, m in shapes), dtype)
+        ws_bytes = lib.pyg_hip_grouped_matmul_dw_workspace_size(c.addressof(descs), len(shapes))
+        ws = g.ws(ws_bytes)
+        uniform = int(len({(k, m) for _, k, m in shapes}) == 1)
+        route = route.format('bf16' if dtype == torch.bfloat16 else 'f32')
+        assert _dw_route(lib, dtype, shapes[0][1], shapes[0][2], uniform, operands, pool.data_ptr()) == route
+        before = _dw_counters(lib)
+        ok(lib, lib.pyg_hip_grouped_matmul_dw(CODE[dtype], c.addressof(descs), len(shapes), pool.data_ptr(), ptr(ws), ws_bytes,
+                                              stream()))
+        torch.cuda.synchronize()
+        after = _dw_counters(lib)
+        assert (after[0] - before[0], after[1] - before[1]) == ((0, 1) if route == 'gen' else (1, 0))
+        g.check()
+        assert_no_poison(pool, 'grouped_matmul_dw pool')
+        close(pool, torch.cat(wants), max(TOL[dtype][0], 1e-5), 1e-4 if dtype == torch.float32 else 0.12, what='grouped dw ' + route)
 
 
 # ---- scatter / gather_coo --------------------------------------------------------------------------------------------------

@@ -643,7 +643,8 @@ def test_full_size_c2_properties():
 
 # ---- weight gradient kernel (csrc/hip/matmul_dw.hip) ---------------------------------
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16, torch.float32])
-@pytest.mark.parametrize('K,M', [(128, 128), (64, 64), (128, 64), (64, 128), (256, 256), (128, 256), (256, 512)])
+@pytest.mark.parametrize('K,M', [(128, 128), (64, 64), (128, 64), (64, 128), (256, 256), (128, 256), (256, 512), (256, 64),
+                                 (256, 192)])
 def test_segment_matmul_weight_gradient_kernel(dtype, K, M):
     # ragged relations incl. empty ones, sizes that are not tile multiples, one relation > many tiles
     sizes = [0, 37, 128, 129, 1000, 0, 5000, 31, 257]
