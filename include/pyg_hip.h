@@ -57,6 +57,8 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  15: pyg_hip_fps / _fps_route / _fps_last_route / _fps_tile / _fps_workspace_size / _fps_pending_error, pyg_hip_grid_cluster /
+ *      _grid_cluster_workspace_size (point-cloud downsampling).
  *  14: pyg_hip_matmul_dw_route (which weight-gradient kernel serves a call, asked without running); a host `ptr` of
  *      pyg_hip_segment_matmul_dw is validated, pyg_hip_matmul_dw_counters count calls that returned PYG_HIP_OK.
  *  13: pyg_hip_knn / _knn_emit, pyg_hip_radius / _radius_emit, pyg_hip_nearest, pyg_hip_spatial_route / _last_route / _tile /
@@ -74,7 +76,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 14
+#define PYG_HIP_ABI_VERSION 15
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -957,6 +959,94 @@ PYG_HIP_API int pyg_hip_nearest(int dtype, const void* x, int64_t N, const void*
                                 const int64_t* ptr_y, int64_t num_examples, int flags, void* workspace, size_t workspace_bytes,
                                 int64_t* out, void* stream);
 PYG_HIP_API int pyg_hip_nearest_pending_error(void);
+
+/* ---- fps, grid_cluster: point-cloud downsampling -------------------------------------------------------------------
+ *
+ * Replace pyg::fps and pyg::grid_cluster (schemas ops/fps.cpp, ops/cluster.cpp; CUDA ops/cuda/{fps,cluster}_kernel.cu).
+ *
+ * fps -- farthest point sampling.  src [N, D] row-major, one floating `dtype` (PYG_F32 / F64 / F16 / BF16), 1 <= D <= 4096;
+ * ptr: int64 [B + 1] on the device, example b owns the points ptr[b] .. ptr[b + 1]; out_ptr: int64 [B] on the device, the
+ * running sum of the per-example sample counts (the reference's cumsum: example b writes out[out_ptr[b - 1] .. out_ptr[b]),
+ * out_ptr[-1] read as 0); start: int64 [B] on the device, the local index of every example's first sample, clamped into its
+ * example (NULL: zeros).  out: int64 [out_total], global point indices, example after example.
+ *   distance   squared Euclidean, dist = 0; for d = 0 .. D-1: diff = a[d] - b[d]; dist = dist + diff * diff -- every operation
+ *              rounded on its own, NO fused multiply-add, in fp32 (fp64 for PYG_F64; 16-bit inputs are widened exactly): the
+ *              arithmetic of knn / radius / nearest.
+ *   running    run[i] = dist(i, first sample); after every further sample s: new = dist(i, s); run[i] = new < run[i] ? new : run[i].
+ *              A point whose first distance is NaN keeps a NaN.
+ *   next       the point with the largest run[i]; among equals the lowest index; a NaN ranks below every number.  Once all
+ *              running distances are 0 (duplicates, an exhausted example) the example's lowest index repeats, as an argmax over
+ *              zeros does.
+ * An example without points writes nothing.  No atomics: every route, every call and the CPU key give the same bits.
+ * N < 2^31 (PYG_HIP_ERR_UNSUPPORTED otherwise, and for D > 4096).
+ *
+ * The caller promises max_points >= the largest example and max_samples >= the largest count (they size the launch; the
+ * binding computes both on the device and reads them back in one copy).  Nothing outside a buffer is ever touched: pointer
+ * entries are clamped into [0, N], write offsets into [0, out_total], an example longer than max_points is cut to it, and no
+ * example writes more than max_samples indices.  Any of these, a ptr that decreases, does not begin at 0 or does not end at N,
+ * sets a pinned word of the device -- fps never synchronises --: the NEXT pyg_hip_fps call on that device fails with
+ * PYG_HIP_ERR_INVALID, and pyg_hip_fps_pending_error() returns and clears the word (meaningful once the stream has been
+ * synchronised).
+ *
+ * Routes.  pyg_hip_fps_route(dtype, B, D, max_points, max_samples, flags) answers, without touching a device, which route a
+ * call takes (PYG_HIP_FPS_ROUTE_*); pyg_hip_fps_last_route() names what the last call on this thread ran:
+ * "resident <d4|lds|glob> t<threads>", "stream <d4|glob>" or "multi <d4|glob> g<blocks per example>".
+ *   resident   one workgroup per example, 64 .. 1024 threads picked from max_points; a thread keeps the running distances of its
+ *              PYG_HIP_FPS_TILE_POINTS points in registers for the whole call and an iteration costs ONE barrier.  d4 (D <= 4):
+ *              the coordinates live in registers too and the winner's travel with its key; lds / glob (any D): they are
+ *              re-read every iteration from an LDS copy of the example while it fits PYG_HIP_FPS_TILE_LDS_BYTES, else from
+ *              global memory.
+ *   stream     max_points above the resident capacity (1024 * PYG_HIP_FPS_TILE_POINTS): the same loop with 1024 threads, the
+ *              running distances in the workspace.
+ *   multi      fewer than PYG_HIP_FPS_TILE_MULTI_EXAMPLES examples AND max_points >= PYG_HIP_FPS_TILE_MULTI_POINTS: one plain
+ *              launch per sample with grid (G, B); every block first reduces the G partial keys of the previous launch
+ *              (redundantly: no second launch, no spin, no grid barrier), block 0 writes the sample, then the block updates
+ *              its slice of the running distances and leaves its partial key for the next launch.  max_samples launches, no
+ *              synchronisation.
+ * PYG_HIP_FPS_FORCE_RESIDENT / _STREAM / _MULTI override the rule (tests, measurements): a forced resident call whose
+ * max_points exceeds the capacity takes `stream`; a forced multi call cuts slices as short as PYG_HIP_FPS_TILE_SLICE_FORCED
+ * points so that small inputs span several blocks.  pyg_hip_fps_tile(which) returns the constants (PYG_HIP_FPS_TILE_*).
+ * workspace: pyg_hip_fps_workspace_size(...) bytes for the same arguments and flags, 16-byte aligned.
+ *
+ * grid_cluster -- voxel ids.  pos [N, D] row-major in `dtype` (the same four), size / start / end [D] in the same dtype on the
+ * device; start == NULL: the column minimum of pos, end == NULL: the column maximum (a NaN in a column makes its bound NaN, as
+ * torch.min / torch.max).  With R = rounding to `dtype` (the identity for F32 / F64, whose arithmetic is fp32 / fp64; the
+ * 16-bit types compute in fp32 and round after each operation):
+ *   q_d = int64(trunc(R(R(pos_d - start_d) / size_d))),  n_d = int64(trunc(R(R(end_d - start_d) / size_d))) + 1,
+ *   out[i] = sum_d q_d * prod_{e < d} n_e   in wrapping int64 -- the reference's CUDA kernel, and its CPU kernel for D >= 2.
+ * int64() of a NaN is 0 and saturates outside the int64 range (on the CPU key too); such ids mean nothing, and no address
+ * depends on them.  One launch when both bounds are given; otherwise a first launch leaves per-block column minima / maxima in
+ * the workspace and the second one reduces them in its prologue (every block, redundantly; no atomics).  Never synchronises.
+ * workspace: pyg_hip_grid_cluster_workspace_size(dtype, N, D, have_start, have_end) bytes (0 when both bounds are given).
+ */
+#define PYG_HIP_FPS_FORCE_RESIDENT 1
+#define PYG_HIP_FPS_FORCE_STREAM 2
+#define PYG_HIP_FPS_FORCE_MULTI 3
+#define PYG_HIP_FPS_FORCE_MASK 3
+#define PYG_HIP_FPS_ROUTE_UNSUPPORTED 0
+#define PYG_HIP_FPS_ROUTE_RESIDENT 1
+#define PYG_HIP_FPS_ROUTE_STREAM 2
+#define PYG_HIP_FPS_ROUTE_MULTI 3
+#define PYG_HIP_FPS_TILE_POINTS 0         /* points per thread of the resident route */
+#define PYG_HIP_FPS_TILE_MIN_THREADS 1    /* smallest resident workgroup */
+#define PYG_HIP_FPS_TILE_MAX_THREADS 2    /* largest resident workgroup; the stream route's */
+#define PYG_HIP_FPS_TILE_SLICE_FORCED 3   /* shortest slice of a forced multi call */
+#define PYG_HIP_FPS_TILE_LDS_BYTES 4      /* resident, D > 4: the example's points are copied to LDS up to this size */
+#define PYG_HIP_FPS_TILE_MULTI_POINTS 5   /* multi: max_points from here on ... */
+#define PYG_HIP_FPS_TILE_MULTI_EXAMPLES 6 /* ... and fewer examples than this */
+#define PYG_HIP_FPS_TILE_SLICE 7          /* shortest slice the rule cuts */
+PYG_HIP_API int pyg_hip_fps_route(int dtype, int64_t B, int64_t D, int64_t max_points, int64_t max_samples, int flags);
+PYG_HIP_API const char* pyg_hip_fps_last_route(void);
+PYG_HIP_API int pyg_hip_fps_tile(int which);
+PYG_HIP_API size_t pyg_hip_fps_workspace_size(int dtype, int64_t N, int64_t B, int64_t D, int64_t max_points, int64_t max_samples,
+                                              int flags);
+PYG_HIP_API int pyg_hip_fps(int dtype, const void* src, int64_t N, int64_t D, const int64_t* ptr, int64_t B, const int64_t* out_ptr,
+                            const int64_t* start, int64_t max_points, int64_t max_samples, int flags, void* workspace,
+                            size_t workspace_bytes, int64_t* out, int64_t out_total, void* stream);
+PYG_HIP_API int pyg_hip_fps_pending_error(void);
+PYG_HIP_API size_t pyg_hip_grid_cluster_workspace_size(int dtype, int64_t N, int64_t D, int have_start, int have_end);
+PYG_HIP_API int pyg_hip_grid_cluster(int dtype, const void* pos, int64_t N, int64_t D, const void* size, const void* start,
+                                     const void* end, void* workspace, size_t workspace_bytes, int64_t* out, void* stream);
 
 /* ---- measurement hooks (bench.py) --------------------------------------------------------- */
 

@@ -12,7 +12,7 @@ _HERE = osp.dirname(osp.abspath(__file__))
 _LIB = None
 
 OK = 0
-ABI_VERSION = 14  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
+ABI_VERSION = 15  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
 DTYPES = {
     torch.float32: 0,
     torch.float64: 1,
@@ -126,6 +126,28 @@ def lib() -> ctypes.CDLL:
         L.pyg_hip_nearest.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p,
                                       c.c_int64, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
         L.pyg_hip_nearest_pending_error.restype = c.c_int
+        # fps / grid_cluster (include/pyg_hip.h, "fps, grid_cluster")
+        # (dtype, B, D, max_points, max_samples, flags)
+        L.pyg_hip_fps_route.restype = c.c_int
+        L.pyg_hip_fps_route.argtypes = [c.c_int, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int]
+        L.pyg_hip_fps_last_route.restype = c.c_char_p
+        L.pyg_hip_fps_tile.restype = c.c_int
+        L.pyg_hip_fps_tile.argtypes = [c.c_int]
+        # (dtype, N, B, D, max_points, max_samples, flags)
+        L.pyg_hip_fps_workspace_size.restype = c.c_size_t
+        L.pyg_hip_fps_workspace_size.argtypes = [c.c_int, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_int]
+        # (dtype, src, N, D, ptr, B, out_ptr, start, max_points, max_samples, flags, workspace, workspace_bytes, out, out_total, stream)
+        L.pyg_hip_fps.restype = c.c_int
+        L.pyg_hip_fps.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p,
+                                  c.c_int64, c.c_int64, c.c_int, c.c_void_p, c.c_size_t, c.c_void_p, c.c_int64, c.c_void_p]
+        L.pyg_hip_fps_pending_error.restype = c.c_int
+        # (dtype, N, D, have_start, have_end)
+        L.pyg_hip_grid_cluster_workspace_size.restype = c.c_size_t
+        L.pyg_hip_grid_cluster_workspace_size.argtypes = [c.c_int, c.c_int64, c.c_int64, c.c_int, c.c_int]
+        # (dtype, pos, N, D, size, start, end, workspace, workspace_bytes, out, stream)
+        L.pyg_hip_grid_cluster.restype = c.c_int
+        L.pyg_hip_grid_cluster.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+                                           c.c_size_t, c.c_void_p, c.c_void_p]
         _LIB = L
     return _LIB
 
@@ -144,6 +166,9 @@ def binding() -> ctypes.CDLL:
         L.pyg_binding_set_spatial_route.restype = None
         L.pyg_binding_set_spatial_route.argtypes = [ctypes.c_int]
         L.pyg_binding_get_spatial_route.restype = ctypes.c_int
+        L.pyg_binding_set_fps_route.restype = None
+        L.pyg_binding_set_fps_route.argtypes = [ctypes.c_int]
+        L.pyg_binding_get_fps_route.restype = ctypes.c_int
         _BINDING = L
     return _BINDING
 

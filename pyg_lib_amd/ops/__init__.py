@@ -567,6 +567,51 @@ def spatial_route(route: Optional[str]):
         _capi.binding().pyg_binding_set_spatial_route(prev)
 
 
+# ---------------------------------------------------------------------------------------------------
+# fps, grid_cluster (csrc/hip/downsample.hip)
+# ---------------------------------------------------------------------------------------------------
+
+def fps(src: Tensor, ptr: Tensor, ratio: float = 0.5, random_start: bool = True) -> Tensor:
+    """Farthest point sampling inside every example (interface of the reference's ``pyg_lib.ops.fps``).
+
+    ``src`` is ``[N, ...]`` (viewed as ``[N, D]``; float32, float64, float16 or bfloat16), ``ptr`` an int64 CSR pointer of
+    ``B + 1`` entries on the same device, ``ratio`` in ``(0, 1]``.  Example ``b`` contributes ``ceil(float32(n_b) * ratio)``
+    global point indices: its first sample is point 0 of the example, or a point drawn from the device's default generator
+    (``random_start``); every further sample is the point farthest (squared Euclidean distance, summed in fp32 -- fp64 for
+    float64 -- without fused multiply-add) from the samples so far, the lowest index among equals.  HIP and CPU tensors give
+    the same bits.  An example without points contributes nothing.  One small device-to-host copy per call (the sizes); a
+    ``ptr`` that is not non-decreasing from 0 to ``N`` raises."""
+    return torch.ops.pyg.fps(src, ptr, ratio, random_start)
+
+
+def grid_cluster(pos: Tensor, size: Tensor, start: Optional[Tensor] = None, end: Optional[Tensor] = None) -> Tensor:
+    """The voxel id of every point of ``pos`` ``[N, ...]`` (viewed as ``[N, D]``) on a regular grid of cell ``size`` ``[D]``
+    between ``start`` and ``end`` ``[D]`` (default: the column minima / maxima of ``pos``), as int64 ``[N]`` (interface of the
+    reference's ``pyg_lib.ops.grid_cluster``).  ``size``, ``start`` and ``end`` have ``pos``'s dtype and device.  Never
+    synchronises: it can be captured into a graph."""
+    return torch.ops.pyg.grid_cluster(pos, size, start, end)
+
+
+def fps_last_route() -> str:
+    """What the last ``fps`` call made from the calling thread on a HIP device ran: ``'resident <d4|lds|glob> t<threads>'``,
+    ``'stream <d4|glob>'`` or ``'multi <d4|glob> g<blocks>'`` (test / diagnostic hook; the rules are in include/pyg_hip.h)."""
+    return _capi.lib().pyg_hip_fps_last_route().decode()
+
+
+@contextlib.contextmanager
+def fps_route(route: Optional[str]):
+    """Context manager: the ``fps`` calls of this thread take the ``'resident'``, ``'stream'`` or ``'multi'`` route whatever
+    their sizes (``None``: the library's rule).  For tests and measurements; a forced ``'resident'`` call whose largest
+    example exceeds the resident capacity takes ``'stream'``, a forced ``'multi'`` call cuts slices of at least 64 points."""
+    flags = {None: 0, 'resident': 1, 'stream': 2, 'multi': 3}[route]   # PYG_HIP_FPS_FORCE_*
+    prev = _capi.binding().pyg_binding_get_fps_route()
+    _capi.binding().pyg_binding_set_fps_route(flags)
+    try:
+        yield
+    finally:
+        _capi.binding().pyg_binding_set_fps_route(prev)
+
+
 __all__ = [
     'grouped_matmul',
     'segment_matmul',
@@ -578,6 +623,8 @@ __all__ = [
     'knn',
     'radius',
     'nearest',
+    'fps',
+    'grid_cluster',
     'index_sort',
     'scatter',
     'scatter_sum',
