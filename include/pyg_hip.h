@@ -57,6 +57,9 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  16: pyg_hip_spline_basis / _basis_backward / _weighting / _weighting_backward_x / _weighting_backward_weight /
+ *      _weighting_backward_basis, pyg_hip_spline_backward_x_workspace_size / _backward_weight_workspace_size,
+ *      pyg_hip_spline_route / _last_route / _tile / _pending_error (the operators behind SplineConv).
  *  15: pyg_hip_fps / _fps_route / _fps_last_route / _fps_tile / _fps_workspace_size / _fps_pending_error, pyg_hip_grid_cluster /
  *      _grid_cluster_workspace_size (point-cloud downsampling).
  *  14: pyg_hip_matmul_dw_route (which weight-gradient kernel serves a call, asked without running); a host `ptr` of
@@ -76,7 +79,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 15
+#define PYG_HIP_ABI_VERSION 16
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -1047,6 +1050,97 @@ PYG_HIP_API int pyg_hip_fps_pending_error(void);
 PYG_HIP_API size_t pyg_hip_grid_cluster_workspace_size(int dtype, int64_t N, int64_t D, int have_start, int have_end);
 PYG_HIP_API int pyg_hip_grid_cluster(int dtype, const void* pos, int64_t N, int64_t D, const void* size, const void* start,
                                      const void* end, void* workspace, size_t workspace_bytes, int64_t* out, void* stream);
+
+/* ---- spline_basis, spline_weighting: the operators behind SplineConv ------------------------------------------------
+ *
+ * Replace the six pyg::spline_* operators (schemas ops/spline.cpp; CPU ops/cpu/spline_kernel.cpp; CUDA ops/cuda/spline_kernel.cu).
+ * All tensors row-major and contiguous.  weight_index and kernel_size are int64, is_open_spline is uint8, all on the device.
+ *
+ * basis -- pseudo [E, D] in PYG_F32 / PYG_F64 (others: PYG_HIP_ERR_INVALID), degree 1, 2 or 3, D <= 16, S = (degree + 1)^D;
+ * outputs basis [E, S] and weight_index [E, S].  For pair (e, s), with k = s, wi = 0, offset = 1, b = 1, for d = 0 .. D-1:
+ *   k_mod = k % (degree + 1), k /= degree + 1
+ *   v  = pseudo[e, d] * T(kernel_size[d] - degree * is_open_spline[d])          (the integer converted to the dtype)
+ *   wi += ((int64(v) + k_mod) % kernel_size[d]) * offset, offset *= kernel_size[d]   (C truncation and C remainder: a pseudo
+ *        outside [0, 1] can give a negative index, as in the reference; kernel_size[d] == 0 contributes 0)
+ *   v -= floor(v);  b *= B(v, k_mod)
+ * B is the uniform B-spline piece of the degree and B' (basis_backward) its derivative, written with the reference's double
+ * literals, so that the promotion rules decide what is evaluated in double and rounded once exactly as there; no fused
+ * multiply-add.  basis_backward: grad_pseudo[e, d] = (sum over s, in order, of B'(v_d) * prod_{d' != d} B(v_d') * grad_basis[e, s])
+ * * T(kernel_size[d] - degree * is_open_spline[d]), the product running over d' in ascending order.  One launch each, one
+ * thread per (e, s) / (e, d), no synchronisation.  The CPU key computes the same bits.
+ *
+ * weighting -- x [E, M_in], weight [K, M_in, M_out], basis / weight_index [E, S], PYG_F32 / PYG_F64 / PYG_BF16.  Every sum is
+ * sequential from +0 in the order written, every product rounded on its own (no fused multiply-add), no atomics:
+ *   forward          out[e, o]  = sum_s sum_i  w[wi, i, o] * (b[e, s] * x[e, i])
+ *   backward_x       gx[e, i]   = sum_o sum_s  (g[e, o] * b[e, s]) * w[wi, i, o]
+ *   backward_basis   gb[e, s]   = sum_o  g[e, o] * (sum_i w[wi, i, o] * x[e, i])
+ *   backward_weight  gw[k, i, o] = sum over the pairs (e, s) with wi == k, in order of e then s, of (g[e, o] * b[e, s]) * x[e, i]
+ * PYG_F32 / PYG_F64: the bits of the CPU key (backward_weight: for every weight of at most PYG_HIP_SPLINE_TILE_CHUNK pairs; a
+ * longer one is summed chunk by chunk and the chunk sums are added in chunk order -- the same bits on every device and every
+ * call, within gamma_(n+2) * sum|terms| of the exact sum).  PYG_BF16: the sums are kept in fp32 (the products of bfloat16
+ * inputs are exact there) and rounded once at the end; the CPU key rounds every step to bfloat16 as the reference does.
+ *
+ * forward, backward_x and backward_basis are one kernel template: a 256-thread workgroup owns a tile of edges, lanes run along
+ * the contiguous axis of the weights (backward_x first writes the transposed weights into its workspace), the tile's rows,
+ * basis and weight_index go through LDS.  Two routes, pyg_hip_spline_route(dtype, E, S, M_in, M_out, K) -- pure, no device:
+ *   global   the rule's answer for every supported shape: one workgroup per tile, the weights come through L2;
+ *   lds      only when forced (PYG_HIP_SPLINE_FORCE_LDS) and K * M_in * M_out elements fit PYG_HIP_SPLINE_TILE_LDS_BYTES: one
+ *            persistent workgroup per compute unit stages the whole weight tensor into LDS once and reads it from there.
+ *            Measured slower than global from 4 096 edges on, 2.5 times at 1 M (one wave per SIMD), hence
+ *            never the rule's choice.
+ * Both give the same bits.  `flags`: PYG_HIP_SPLINE_FORCE_LDS / _GLOBAL (tests, measurements; a forced lds call whose weights
+ * do not fit runs global).  pyg_hip_spline_last_route() names what the last weighting call of this thread
+ * ran: "<forward|backward_x|backward_basis> <lds|global> tx<lanes per edge> te<edges per tile>".  An edge whose rows exceed
+ * the LDS tile (PYG_HIP_SPLINE_TILE_EDGE_BYTES; thousands of channels): PYG_HIP_ERR_UNSUPPORTED.
+ *
+ * backward_weight: the E * S pair positions are stably sorted by weight index (pyg_hip_index_sort's kernels; an index outside
+ * [0, K) is keyed K, a bucket nobody reads), one workgroup finds the row starts, one launch deals (weight, chunk of
+ * PYG_HIP_SPLINE_TILE_CHUNK consecutive sorted pairs, 64 x 64 tile of the matrix) work items whose threads keep their sums in
+ * registers; a weight of one chunk is written straight to grad_weight, a longer one through per-chunk slabs in the workspace
+ * that a second launch adds in chunk order; weights without pairs are written as zeros (no memset).  `flags` bits 8 .. 12:
+ * log2 of the chunk of this call, 9 .. 12 (0: the constant; a measurement hook -- the bits of long weights depend on it).
+ *
+ * A weight_index outside [0, K) never causes an access outside a buffer: the pair contributes nothing and a pinned word of the
+ * device is set -- no operator here synchronises --: the NEXT pyg_hip_spline_* call on that device fails with
+ * PYG_HIP_ERR_INVALID, and pyg_hip_spline_pending_error() returns and clears the word (meaningful once the stream has been
+ * synchronised).  Workspaces: the sizes below, 16-byte aligned; less is PYG_HIP_ERR_WORKSPACE.
+ */
+#define PYG_HIP_SPLINE_FORCE_LDS 1
+#define PYG_HIP_SPLINE_FORCE_GLOBAL 2
+#define PYG_HIP_SPLINE_FORCE_MASK 3
+#define PYG_HIP_SPLINE_ROUTE_UNSUPPORTED 0
+#define PYG_HIP_SPLINE_ROUTE_LDS 1
+#define PYG_HIP_SPLINE_ROUTE_GLOBAL 2
+#define PYG_HIP_SPLINE_TILE_LDS_BYTES 0       /* route lds: the weight tensor fits this many bytes of LDS */
+#define PYG_HIP_SPLINE_TILE_CHUNK 1           /* backward_weight: sorted pairs per work item */
+#define PYG_HIP_SPLINE_TILE_EDGE_BYTES 2      /* LDS of the edge tile */
+#define PYG_HIP_SPLINE_TILE_DW 3              /* backward_weight: side of a work item's matrix tile */
+PYG_HIP_API int pyg_hip_spline_route(int dtype, int64_t E, int64_t S, int64_t M_in, int64_t M_out, int64_t K);
+PYG_HIP_API const char* pyg_hip_spline_last_route(void);
+PYG_HIP_API int pyg_hip_spline_tile(int which);
+PYG_HIP_API int pyg_hip_spline_pending_error(void);
+PYG_HIP_API int pyg_hip_spline_basis(int dtype, const void* pseudo, const int64_t* kernel_size, const uint8_t* is_open_spline,
+                                     int64_t E, int64_t D, int degree, void* basis, int64_t* weight_index, void* stream);
+PYG_HIP_API int pyg_hip_spline_basis_backward(int dtype, const void* grad_basis, const void* pseudo, const int64_t* kernel_size,
+                                              const uint8_t* is_open_spline, int64_t E, int64_t D, int64_t S, int degree,
+                                              void* grad_pseudo, void* stream);
+PYG_HIP_API int pyg_hip_spline_weighting(int dtype, const void* x, const void* weight, const void* basis, const int64_t* weight_index,
+                                         int64_t E, int64_t S, int64_t M_in, int64_t M_out, int64_t K, int flags, void* out,
+                                         void* stream);
+PYG_HIP_API size_t pyg_hip_spline_backward_x_workspace_size(int dtype, int64_t M_in, int64_t M_out, int64_t K);
+PYG_HIP_API int pyg_hip_spline_weighting_backward_x(int dtype, const void* grad_out, const void* weight, const void* basis,
+                                                    const int64_t* weight_index, int64_t E, int64_t S, int64_t M_in, int64_t M_out,
+                                                    int64_t K, int flags, void* workspace, size_t workspace_bytes, void* grad_x,
+                                                    void* stream);
+PYG_HIP_API int pyg_hip_spline_weighting_backward_basis(int dtype, const void* grad_out, const void* x, const void* weight,
+                                                        const int64_t* weight_index, int64_t E, int64_t S, int64_t M_in,
+                                                        int64_t M_out, int64_t K, int flags, void* grad_basis, void* stream);
+PYG_HIP_API size_t pyg_hip_spline_backward_weight_workspace_size(int dtype, int64_t E, int64_t S, int64_t M_in, int64_t M_out,
+                                                                 int64_t K, int flags);
+PYG_HIP_API int pyg_hip_spline_weighting_backward_weight(int dtype, const void* grad_out, const void* x, const void* basis,
+                                                         const int64_t* weight_index, int64_t E, int64_t S, int64_t M_in,
+                                                         int64_t M_out, int64_t K, int flags, void* workspace,
+                                                         size_t workspace_bytes, void* grad_weight, void* stream);
 
 /* ---- measurement hooks (bench.py) --------------------------------------------------------- */
 

@@ -12,7 +12,7 @@ _HERE = osp.dirname(osp.abspath(__file__))
 _LIB = None
 
 OK = 0
-ABI_VERSION = 15  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
+ABI_VERSION = 16  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
 DTYPES = {
     torch.float32: 0,
     torch.float64: 1,
@@ -148,6 +148,41 @@ def lib() -> ctypes.CDLL:
         L.pyg_hip_grid_cluster.restype = c.c_int
         L.pyg_hip_grid_cluster.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
                                            c.c_size_t, c.c_void_p, c.c_void_p]
+        # spline_basis / spline_weighting (include/pyg_hip.h, "spline_basis, spline_weighting")
+        # (dtype, E, S, M_in, M_out, K)
+        L.pyg_hip_spline_route.restype = c.c_int
+        L.pyg_hip_spline_route.argtypes = [c.c_int] + [c.c_int64] * 5
+        L.pyg_hip_spline_last_route.restype = c.c_char_p
+        L.pyg_hip_spline_tile.restype = c.c_int
+        L.pyg_hip_spline_tile.argtypes = [c.c_int]
+        L.pyg_hip_spline_pending_error.restype = c.c_int
+        # (dtype, pseudo, kernel_size, is_open_spline, E, D, degree, basis, weight_index, stream)
+        L.pyg_hip_spline_basis.restype = c.c_int
+        L.pyg_hip_spline_basis.argtypes = [c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int, c.c_void_p,
+                                           c.c_void_p, c.c_void_p]
+        # (dtype, grad_basis, pseudo, kernel_size, is_open_spline, E, D, S, degree, grad_pseudo, stream)
+        L.pyg_hip_spline_basis_backward.restype = c.c_int
+        L.pyg_hip_spline_basis_backward.argtypes = [c.c_int, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64,
+                                                    c.c_int64, c.c_int, c.c_void_p, c.c_void_p]
+        # (dtype, x, weight, basis, weight_index, E, S, M_in, M_out, K, flags, out, stream)
+        L.pyg_hip_spline_weighting.restype = c.c_int
+        L.pyg_hip_spline_weighting.argtypes = [c.c_int] + [c.c_void_p] * 4 + [c.c_int64] * 5 + [c.c_int, c.c_void_p, c.c_void_p]
+        # (dtype, grad_out, x, weight, weight_index, E, S, M_in, M_out, K, flags, grad_basis, stream)
+        L.pyg_hip_spline_weighting_backward_basis.restype = c.c_int
+        L.pyg_hip_spline_weighting_backward_basis.argtypes = L.pyg_hip_spline_weighting.argtypes
+        # (dtype, M_in, M_out, K)
+        L.pyg_hip_spline_backward_x_workspace_size.restype = c.c_size_t
+        L.pyg_hip_spline_backward_x_workspace_size.argtypes = [c.c_int, c.c_int64, c.c_int64, c.c_int64]
+        # (dtype, grad_out, weight, basis, weight_index, E, S, M_in, M_out, K, flags, workspace, workspace_bytes, grad_x, stream)
+        L.pyg_hip_spline_weighting_backward_x.restype = c.c_int
+        L.pyg_hip_spline_weighting_backward_x.argtypes = [c.c_int] + [c.c_void_p] * 4 + [c.c_int64] * 5 + [c.c_int, c.c_void_p, c.c_size_t,
+                                                                                                        c.c_void_p, c.c_void_p]
+        # (dtype, E, S, M_in, M_out, K, flags)
+        L.pyg_hip_spline_backward_weight_workspace_size.restype = c.c_size_t
+        L.pyg_hip_spline_backward_weight_workspace_size.argtypes = [c.c_int] + [c.c_int64] * 5 + [c.c_int]
+        # (dtype, grad_out, x, basis, weight_index, E, S, M_in, M_out, K, flags, workspace, workspace_bytes, grad_weight, stream)
+        L.pyg_hip_spline_weighting_backward_weight.restype = c.c_int
+        L.pyg_hip_spline_weighting_backward_weight.argtypes = L.pyg_hip_spline_weighting_backward_x.argtypes
         _LIB = L
     return _LIB
 
@@ -169,6 +204,9 @@ def binding() -> ctypes.CDLL:
         L.pyg_binding_set_fps_route.restype = None
         L.pyg_binding_set_fps_route.argtypes = [ctypes.c_int]
         L.pyg_binding_get_fps_route.restype = ctypes.c_int
+        L.pyg_binding_set_spline_route.restype = None
+        L.pyg_binding_set_spline_route.argtypes = [ctypes.c_int]
+        L.pyg_binding_get_spline_route.restype = ctypes.c_int
         _BINDING = L
     return _BINDING
 

@@ -612,6 +612,58 @@ def fps_route(route: Optional[str]):
         _capi.binding().pyg_binding_set_fps_route(prev)
 
 
+# ---------------------------------------------------------------------------------------------------
+# spline_basis, spline_weighting (csrc/hip/spline.hip)
+# ---------------------------------------------------------------------------------------------------
+
+def spline_basis(pseudo: Tensor, kernel_size: Tensor, is_open_spline: Tensor, degree: int = 1) -> Tuple[Tensor, Tensor]:
+    """The B-spline basis of ``SplineConv`` (interface of the reference's ``pyg_lib.ops.spline_basis``).
+
+    ``pseudo`` is ``[E, D]`` pseudo-coordinates in ``[0, 1]``, ``kernel_size`` an int64 ``[D]`` and ``is_open_spline`` a uint8
+    ``[D]`` tensor on its device, ``degree`` 1, 2 or 3.  Returns ``basis`` ``[E, (degree + 1)^D]`` in ``pseudo``'s dtype
+    (differentiable in ``pseudo``) and the int64 ``weight_index`` of the same shape.  float32 and float64 on a HIP device
+    (bfloat16 too on the CPU); both devices give the same bits.  Never synchronises."""
+    return torch.ops.pyg.spline_basis(pseudo, kernel_size, is_open_spline, degree)
+
+
+def spline_weighting(x: Tensor, weight: Tensor, basis: Tensor, weight_index: Tensor) -> Tensor:
+    """``out[e] = sum_s basis[e, s] * (x[e] @ weight[weight_index[e, s]])`` (interface of the reference's
+    ``pyg_lib.ops.spline_weighting``): ``x`` ``[E, M_in]``, ``weight`` ``[K, M_in, M_out]``, ``basis`` / ``weight_index``
+    ``[E, S]``; differentiable in ``x``, ``weight`` and ``basis``.  float32, float64 and bfloat16.  No atomics anywhere: float32
+    and float64 results have the bits of the CPU key (the weight gradient: for weights of up to 1024 pairs; bounded and
+    reproducible beyond).  Never synchronises: on a HIP device a ``weight_index`` outside ``[0, K)`` contributes nothing and is
+    reported by the NEXT spline call on that device (:func:`spline_pending_error`); on the CPU it raises."""
+    return torch.ops.pyg.spline_weighting(x, weight, basis, weight_index)
+
+
+def spline_last_route() -> str:
+    """What the last ``spline_weighting`` forward, ``backward_x`` or ``backward_basis`` made from the calling thread on a HIP
+    device ran: ``'<forward|backward_x|backward_basis> <lds|global> tx<lanes> te<edges>'`` (test / diagnostic hook; the rule is
+    in include/pyg_hip.h)."""
+    return _capi.lib().pyg_hip_spline_last_route().decode()
+
+
+@contextlib.contextmanager
+def spline_route(route: Optional[str]):
+    """Context manager: the ``spline_weighting`` operators called from this thread take the ``'lds'`` or the ``'global'`` route
+    (``None``: the library's rule, which is ``'global'`` for every shape -- ``'lds'`` measured slower and runs only when
+    forced).  For tests and measurements; a forced ``'lds'`` call whose weights do not fit the LDS budget runs ``'global'``.
+    Autograd's backward runs on its own thread and keeps the rule."""
+    flags = {None: 0, 'lds': 1, 'global': 2}[route]   # PYG_HIP_SPLINE_FORCE_*
+    prev = _capi.binding().pyg_binding_get_spline_route()
+    _capi.binding().pyg_binding_set_spline_route(flags)
+    try:
+        yield
+    finally:
+        _capi.binding().pyg_binding_set_spline_route(prev)
+
+
+def spline_pending_error() -> int:
+    """Returns and clears the word a spline call on the current HIP device sets when it meets a ``weight_index`` outside
+    ``[0, K)`` (non-zero: there was one).  Meaningful once the stream has been synchronised."""
+    return int(_capi.lib().pyg_hip_spline_pending_error())
+
+
 __all__ = [
     'grouped_matmul',
     'segment_matmul',
@@ -625,6 +677,8 @@ __all__ = [
     'nearest',
     'fps',
     'grid_cluster',
+    'spline_basis',
+    'spline_weighting',
     'index_sort',
     'scatter',
     'scatter_sum',
