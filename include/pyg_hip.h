@@ -57,6 +57,8 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  17: pyg_hip_graclus / _graclus_route / _graclus_last_route / _graclus_tile / _graclus_workspace_size / _graclus_pending_error
+ *      (greedy graph matching in parallel rounds).
  *  16: pyg_hip_spline_basis / _basis_backward / _weighting / _weighting_backward_x / _weighting_backward_weight /
  *      _weighting_backward_basis, pyg_hip_spline_backward_x_workspace_size / _backward_weight_workspace_size,
  *      pyg_hip_spline_route / _last_route / _tile / _pending_error (the operators behind SplineConv).
@@ -79,7 +81,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 16
+#define PYG_HIP_ABI_VERSION 17
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -1141,6 +1143,77 @@ PYG_HIP_API int pyg_hip_spline_weighting_backward_weight(int dtype, const void* 
                                                          const int64_t* weight_index, int64_t E, int64_t S, int64_t M_in,
                                                          int64_t M_out, int64_t K, int flags, void* workspace,
                                                          size_t workspace_bytes, void* grad_weight, void* stream);
+
+/* ---- graclus_cluster: greedy matching in random order, in parallel rounds --------------------------------------------
+ *
+ * Replaces pyg::graclus_cluster (schema ops/graclus.cpp; CPU ops/cpu/graclus_kernel.cpp; CUDA ops/cuda/graclus_kernel.cu).
+ * rowptr [N + 1] and col [E]: int64 CSR on the device; weight [E] in `weight_dtype` (PYG_F32 / F64 / F16 / BF16; 16-bit
+ * weights are widened exactly for the comparisons) or NULL with weight_dtype PYG_HIP_GRACLUS_NO_WEIGHT; perm [N]: int64, a
+ * permutation of 0 .. N-1; out [N]: int64.  N < 2^31 (PYG_HIP_ERR_UNSUPPORTED otherwise).
+ *
+ * The operator is the reference's sequential CPU loop: with out = -1 everywhere, visit u = perm[0], perm[1], ...; a node with
+ * out[u] >= 0 is skipped; otherwise
+ *   without weights  u takes the first entry x of its row, in CSR order, with x != u and out[x] < 0;
+ *   with weights     u takes, among the entries x with out[x] < 0 and weight >= 0, the one of the largest weight, the LAST one
+ *                    among equals (NaN and negative weights never win, -0.0 and +inf do; a self loop can win, then u stays alone);
+ * and out[u] = out[x] = min(u, x), or out[u] = u when there is no such entry.
+ *
+ * Every route computes exactly that in rounds.  rank = the inverse of perm.  A node is active while out[u] < 0.  A candidate of
+ * an active u is a row entry x with out[x] < 0 and (without weights) x != u, (with weights) weight >= 0.  Per round:
+ *   phase A  every active u offers rank(u) to m[x] of every candidate x and to m[u]; m[.] is the minimum of the round's offers
+ *            (an integer maximum of `round * 2^32 + (2^32 - 1 - rank)`: no clearing, no dependence on thread order); u records
+ *            its pick p(u) by the rule above, or none;
+ *   phase B  u is ready iff rank(u) == m[u] and (p(u) is none or rank(u) == m[p(u)]); a ready u writes out[u] = out[p] =
+ *            min(u, p), or out[u] = u without a pick.  The others wait for the next round.
+ * A ready u is the earliest node that can still reach u or p(u), so what it sees is what the sequential visit sees at u; two ready
+ * nodes never share a node, so phase B has no write conflict; the active node of the smallest rank is always ready, so at most N
+ * rounds run.  The round count is a function of the input alone: the same on every route and in tests/_graclus_ref.py.
+ *
+ * Routes.  pyg_hip_graclus_route(N, E, flags) answers, without touching a device, which route a call takes
+ * (PYG_HIP_GRACLUS_ROUTE_*; 0 for N or E negative or N >= 2^31):
+ *   single   N <= PYG_HIP_GRACLUS_TILE_SINGLE_NODES and E <= PYG_HIP_GRACLUS_TILE_SINGLE_EDGES: ONE launch of one workgroup of
+ *            PYG_HIP_GRACLUS_TILE_SINGLE_THREADS threads that strides over the nodes in both phases, a workgroup barrier between
+ *            them; it counts the nodes still active itself.  No host read: capturable into a graph.
+ *   multi    two launches per round over all nodes (PYG_HIP_GRACLUS_TILE_MULTI_THREADS threads per workgroup), enqueued in
+ *            batches of PYG_HIP_GRACLUS_TILE_BATCH rounds.  Phase B subtracts what it matched from the round's word of active
+ *            nodes (one integer atomic per workgroup); every launch returns at once when the previous round's word is zero.
+ *            After each batch the host reads the word back through pinned memory -- the call SYNCHRONISES the stream, once per
+ *            batch -- and enqueues another batch if nodes are left.  No grid barrier, no cooperative launch, no spinning.
+ * PYG_HIP_GRACLUS_FORCE_SINGLE / _MULTI override the rule (tests, measurements); a forced single call above the capacity
+ * (PYG_HIP_GRACLUS_TILE_SINGLE_MAX_NODES nodes or _SINGLE_MAX_EDGES edges) runs multi.  The rule's thresholds are the measured
+ * cross-over.  pyg_hip_graclus_last_route() names what the last call of this thread ran:
+ * "<single|multi> r<rounds> b<read-backs>" (single: the rounds come from a pinned word the kernel writes, so the text is
+ * meaningful once the stream has been synchronised; its read-backs are 0), "none r0 b0" for N == 0.
+ * pyg_hip_graclus_tile(which) returns the constants.  workspace: pyg_hip_graclus_workspace_size(N, E, flags) bytes, 16-byte
+ * aligned (32-bit state, rank and pick and the 64-bit m of every node).
+ *
+ * Bad input never causes an access outside a buffer: a col entry outside [0, N) is no candidate and forms no address, a row
+ * range is clamped into [0, E], a perm entry outside [0, N) is dropped and a node whose rank nobody wrote (a repeated entry)
+ * is ranked behind all others.  Any of these sets a pinned word of the device: the NEXT pyg_hip_graclus call on that device
+ * fails with PYG_HIP_ERR_INVALID, and pyg_hip_graclus_pending_error() returns and clears the word (meaningful once the stream
+ * has been synchronised).  The result of such a call is unspecified, but every out[u] is written.
+ */
+#define PYG_HIP_GRACLUS_NO_WEIGHT (-1)
+#define PYG_HIP_GRACLUS_FORCE_SINGLE 1
+#define PYG_HIP_GRACLUS_FORCE_MULTI 2
+#define PYG_HIP_GRACLUS_FORCE_MASK 3
+#define PYG_HIP_GRACLUS_ROUTE_UNSUPPORTED 0
+#define PYG_HIP_GRACLUS_ROUTE_SINGLE 1
+#define PYG_HIP_GRACLUS_ROUTE_MULTI 2
+#define PYG_HIP_GRACLUS_TILE_SINGLE_NODES 0     /* single: the rule takes it up to this many nodes ... */
+#define PYG_HIP_GRACLUS_TILE_SINGLE_EDGES 1     /* ... and this many edges */
+#define PYG_HIP_GRACLUS_TILE_SINGLE_THREADS 2   /* single: threads of the one workgroup */
+#define PYG_HIP_GRACLUS_TILE_SINGLE_MAX_NODES 3 /* a forced single call runs multi above this many nodes */
+#define PYG_HIP_GRACLUS_TILE_MULTI_THREADS 4    /* multi: threads per workgroup, one node each */
+#define PYG_HIP_GRACLUS_TILE_BATCH 5            /* multi: rounds enqueued between two read-backs */
+#define PYG_HIP_GRACLUS_TILE_SINGLE_MAX_EDGES 6 /* ... or above this many edges */
+PYG_HIP_API int pyg_hip_graclus_route(int64_t N, int64_t E, int flags);
+PYG_HIP_API const char* pyg_hip_graclus_last_route(void);
+PYG_HIP_API int pyg_hip_graclus_tile(int which);
+PYG_HIP_API size_t pyg_hip_graclus_workspace_size(int64_t N, int64_t E, int flags);
+PYG_HIP_API int pyg_hip_graclus(const int64_t* rowptr, const int64_t* col, int weight_dtype, const void* weight, const int64_t* perm,
+                                int64_t N, int64_t E, int flags, void* workspace, size_t workspace_bytes, int64_t* out, void* stream);
+PYG_HIP_API int pyg_hip_graclus_pending_error(void);
 
 /* ---- measurement hooks (bench.py) --------------------------------------------------------- */
 

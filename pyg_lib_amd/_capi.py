@@ -12,7 +12,7 @@ _HERE = osp.dirname(osp.abspath(__file__))
 _LIB = None
 
 OK = 0
-ABI_VERSION = 16  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
+ABI_VERSION = 17  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
 DTYPES = {
     torch.float32: 0,
     torch.float64: 1,
@@ -183,6 +183,20 @@ def lib() -> ctypes.CDLL:
         # (dtype, grad_out, x, basis, weight_index, E, S, M_in, M_out, K, flags, workspace, workspace_bytes, grad_weight, stream)
         L.pyg_hip_spline_weighting_backward_weight.restype = c.c_int
         L.pyg_hip_spline_weighting_backward_weight.argtypes = L.pyg_hip_spline_weighting_backward_x.argtypes
+        # graclus_cluster (include/pyg_hip.h, "graclus_cluster")
+        # (N, E, flags)
+        L.pyg_hip_graclus_route.restype = c.c_int
+        L.pyg_hip_graclus_route.argtypes = [c.c_int64, c.c_int64, c.c_int]
+        L.pyg_hip_graclus_last_route.restype = c.c_char_p
+        L.pyg_hip_graclus_tile.restype = c.c_int
+        L.pyg_hip_graclus_tile.argtypes = [c.c_int]
+        L.pyg_hip_graclus_workspace_size.restype = c.c_size_t
+        L.pyg_hip_graclus_workspace_size.argtypes = [c.c_int64, c.c_int64, c.c_int]
+        # (rowptr, col, weight_dtype, weight, perm, N, E, flags, workspace, workspace_bytes, out, stream)
+        L.pyg_hip_graclus.restype = c.c_int
+        L.pyg_hip_graclus.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int,
+                                      c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
+        L.pyg_hip_graclus_pending_error.restype = c.c_int
         _LIB = L
     return _LIB
 
@@ -207,6 +221,9 @@ def binding() -> ctypes.CDLL:
         L.pyg_binding_set_spline_route.restype = None
         L.pyg_binding_set_spline_route.argtypes = [ctypes.c_int]
         L.pyg_binding_get_spline_route.restype = ctypes.c_int
+        L.pyg_binding_set_graclus_route.restype = None
+        L.pyg_binding_set_graclus_route.argtypes = [ctypes.c_int]
+        L.pyg_binding_get_graclus_route.restype = ctypes.c_int
         _BINDING = L
     return _BINDING
 

@@ -664,6 +664,56 @@ def spline_pending_error() -> int:
     return int(_capi.lib().pyg_hip_spline_pending_error())
 
 
+# ---------------------------------------------------------------------------------------------------
+# graclus_cluster (csrc/hip/graclus.hip)
+# ---------------------------------------------------------------------------------------------------
+
+def graclus_cluster(rowptr: Tensor, col: Tensor, weight: Optional[Tensor] = None) -> Tensor:
+    """Greedy graph matching in random order (interface of the reference's ``pyg_lib.ops.graclus_cluster``): the nodes of the
+    int64 CSR graph ``rowptr`` ``[N + 1]`` / ``col`` ``[E]`` are visited in the order ``torch.randperm(N)`` draws from the
+    generator of their device; an unmatched node takes its first unmatched neighbour -- with ``weight`` ``[E]`` the unmatched
+    neighbour of the largest weight ``>= 0``, the last one among equals -- and both get the cluster id ``min(u, v)``; a node
+    without such a neighbour keeps its own id.  Returns int64 ``[N]``.  See :func:`graclus_cluster_perm`."""
+    return torch.ops.pyg.graclus_cluster(rowptr, col, weight)
+
+
+def graclus_cluster_perm(rowptr: Tensor, col: Tensor, weight: Optional[Tensor], perm: Tensor) -> Tensor:
+    """:func:`graclus_cluster` with the visiting order ``perm`` (an int64 permutation of ``0 .. N-1``) given: the deterministic
+    core.  HIP and CPU tensors give the same output, on every route.  On a HIP device ``weight`` is float32, float64, float16
+    or bfloat16 (the CPU also takes the integer types); the sequential visit is computed exactly in parallel rounds -- one
+    launch for graphs of up to 768 nodes and 8 192 entries (capturable into a graph), two launches per round and one stream synchronisation per 16 rounds for
+    large ones.  There a ``col`` entry outside ``[0, N)``, a ``rowptr`` outside ``[0, E]`` or a ``perm`` that is no permutation
+    touches no memory outside the tensors and is reported by the NEXT graclus call on that device
+    (:func:`graclus_pending_error`); on the CPU it raises."""
+    return torch.ops.pyg.graclus_cluster_perm(rowptr, col, weight, perm)
+
+
+def graclus_last_route() -> str:
+    """What the last graclus call made from the calling thread on a HIP device ran: ``'<single|multi> r<rounds> b<read-backs>'``
+    (test / diagnostic hook; meaningful once the stream has been synchronised; the rule is in include/pyg_hip.h)."""
+    return _capi.lib().pyg_hip_graclus_last_route().decode()
+
+
+@contextlib.contextmanager
+def graclus_route(route: Optional[str]):
+    """Context manager: the graclus calls of this thread take the ``'single'`` or the ``'multi'`` route whatever their sizes
+    (``None``: the library's rule).  For tests and measurements; a forced ``'single'`` call above the capacity of the one
+    workgroup (131 072 nodes or 2 097 152 edges) runs ``'multi'``."""
+    flags = {None: 0, 'single': 1, 'multi': 2}[route]   # PYG_HIP_GRACLUS_FORCE_*
+    prev = _capi.binding().pyg_binding_get_graclus_route()
+    _capi.binding().pyg_binding_set_graclus_route(flags)
+    try:
+        yield
+    finally:
+        _capi.binding().pyg_binding_set_graclus_route(prev)
+
+
+def graclus_pending_error() -> int:
+    """Returns and clears the word a graclus call on the current HIP device sets when it meets a bad ``col``, ``rowptr`` or
+    ``perm`` entry (non-zero: there was one).  Meaningful once the stream has been synchronised."""
+    return int(_capi.lib().pyg_hip_graclus_pending_error())
+
+
 __all__ = [
     'grouped_matmul',
     'segment_matmul',
@@ -679,6 +729,8 @@ __all__ = [
     'grid_cluster',
     'spline_basis',
     'spline_weighting',
+    'graclus_cluster',
+    'graclus_cluster_perm',
     'index_sort',
     'scatter',
     'scatter_sum',
