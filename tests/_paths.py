@@ -1,5 +1,6 @@
-"""Which kernel a shape selects: the selection rules of csr.hip and reduce.hip restated, for the tests that reach every kernel
-path on purpose (tests/test_guard_capi_gpu.py, tests/test_special_values_gpu.py).  A case asserts the path it was built for,
+"""Which kernel a shape selects: the selection rules of csr.hip, reduce.hip and index_sort.hip restated, for the tests that
+reach every kernel path on purpose (tests/test_guard_capi_gpu.py, tests/test_special_values_gpu.py,
+tests/test_index_sort_gpu.py).  A case asserts the path it was built for,
 so a later change of the rules cannot silently empty it."""
 import numpy as np
 import torch
@@ -143,3 +144,26 @@ def softmax_path(dtype, outer, D, inner, groups, backward=False):
     else:
         L = 1
     return f'lanes{L}', 512 * L
+
+
+# ---- index_sort.hip: the head of run_sort restated ----------------------------------------------------------------------------
+def sort_path(dtype, n, min_key, max_key, max_value=None):
+    """(mode, passes, index_bits) of index_sort: `passes` 8-bit digits -- from `max_value` when the caller gives one (keys
+    are then promised to lie in [0, max_value]), every byte of the key when there is a negative key, else from the largest
+    key; `index_bits` the bits of the largest position; 'packed' (key and position in one 64-bit word through
+    scatter_packed_kernel) when the keys count as non-negative and both fit the word, else 'pairs' (scatter_kernel)."""
+    size = torch.empty((), dtype=dtype).element_size()
+
+    def nbytes(m):
+        return max(1, min((max(int(m), 0).bit_length() + 7) // 8, size))
+
+    if max_value is not None:
+        passes, nonneg = nbytes(max_value), True
+    elif min_key < 0:
+        passes, nonneg = size, False
+    else:
+        passes, nonneg = nbytes(max_key), True
+    ib = 1
+    while ib < 63 and (1 << ib) < n:
+        ib += 1
+    return ('packed' if nonneg and 8 * passes + ib <= 64 else 'pairs'), passes, ib
