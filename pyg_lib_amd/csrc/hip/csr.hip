@@ -945,6 +945,17 @@ __global__ __launch_bounds__(256) void softmax_csr_stream_kernel(const T* __rest
 
 // The launches around a row kernel that skips hub rows: hub_begin() in front of it (cut, scratch layout, counters), then the
 // row kernel with st.sc / st.hw, then hub_end().
+// (the counters are cleared by a kernel, not by hipMemsetAsync: a 16-byte memset node between kernel nodes is what faulted on the
+// first replay of a captured fused_scatter_reduce, DESIGN.md "HIP graphs")
+__global__ void hub_clear_kernel(int* __restrict__ counters) {
+  if (threadIdx.x < 4) counters[threadIdx.x] = 0;
+}
+inline int hub_clear(const HubWs& hw, hipStream_t stream) {
+  hipLaunchKernelGGL(hub_clear_kernel, dim3(1), dim3(64), 0, stream, hw.counters);
+  PYG_HIP_CHECK(hipGetLastError());
+  return PYG_HIP_OK;
+}
+
 struct HubStage {
   CsrShape sc;
   HubWs hw;
@@ -960,7 +971,7 @@ int hub_begin(const CsrShape& s, int64_t cut, HubStage& st, hipStream_t stream) 
   if (!st.hubs) return PYG_HIP_OK;
   st.sc.long_cut = cut;
   if (hub_plan(s.hub_ws, s.hub_ws_bytes, s.leading * s.E, s.K, sizeof(acc_t), OP == CSR_MIN || OP == CSR_MAX, &st.hw, &st.max_chunks))
-    PYG_HIP_CHECK(hipMemsetAsync(st.hw.counters, 0, 16, stream));
+    if (int rc_ = hub_clear(st.hw, stream)) return rc_;
   st.max_hubs = s.leading * s.E / cut;   // every hub is longer than the cut
   return PYG_HIP_OK;
 }
@@ -1101,7 +1112,7 @@ int launch_gather(const void* src, const int64_t* indptr, void* out, const CsrSh
   HubWs hw;
   int64_t max_chunks = 0;
   if (hubs && hub_plan(s.hub_ws, s.hub_ws_bytes, s.leading * s.E, s.K, 0, false, &hw, &max_chunks))
-    PYG_HIP_CHECK(hipMemsetAsync(hw.counters, 0, 16, stream));
+    if (int rc_ = hub_clear(hw, stream)) return rc_;
 #define PYG_CSR_LAUNCH(LL)                                                                                  \
   hipLaunchKernelGGL((gather_csr_kernel<T, V, LL>), dim3((unsigned)((items * LL + 255) / 256)), dim3(256), 0, \
                      stream, static_cast<const T*>(src), indptr, static_cast<T*>(out), sc, hw)

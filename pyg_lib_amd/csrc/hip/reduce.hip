@@ -207,6 +207,29 @@ __global__ void fill_kernel(T* out, int64_t n, T v) {
   if (i < n) out[i] = v;
 }
 
+// `bytes` zero bytes at `p`, any alignment: 16-byte stores where the address allows, single bytes at both ends.  The atomic
+// routes clear a fresh sum's `out` with this kernel and not with hipMemsetAsync: recorded into a HIP graph, the memset node in
+// front of the atomic kernel did not clear `out` on replay (tests/test_graph_replay_gpu.py: garbage plus the sums), the same
+// pattern as the hub counters of fused_reduce.hip and csr.hip ("HIP graphs").
+__global__ void zero_bytes_kernel(unsigned char* __restrict__ p, size_t bytes) {
+  const size_t to_16 = (16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15;
+  const size_t head = to_16 < bytes ? to_16 : bytes;
+  const size_t body = (bytes - head) / 16;
+  const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, nth = gridDim.x * (size_t)blockDim.x;
+  uint4* q = reinterpret_cast<uint4*>(p + head);
+  for (size_t i = tid; i < body; i += nth) q[i] = make_uint4(0, 0, 0, 0);
+  for (size_t i = tid; i < head; i += nth) p[i] = 0;
+  for (size_t i = head + body * 16 + tid; i < bytes; i += nth) p[i] = 0;
+}
+inline int zero_bytes(void* p, size_t bytes, hipStream_t stream) {
+  const size_t want = (bytes / 16 + 255) / 256 + 1;
+  const size_t cap = (size_t)device_info().num_cus * 8;
+  hipLaunchKernelGGL(zero_bytes_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, stream,
+                     static_cast<unsigned char*>(p), bytes);
+  PYG_HIP_CHECK(hipGetLastError());
+  return PYG_HIP_OK;
+}
+
 __global__ void fill_i64_kernel(int64_t* out, int64_t n, int64_t v) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < n) out[i] = v;
@@ -690,11 +713,12 @@ int run_scatter(Route route, int op, int dtype, const void* src, const int64_t* 
   }
   // PYG_HIP_SCATTER_FRESH_SUM: `out` of a sum is uninitialised.  The rows routes write every slot and never read it; the
   // atomic routes accumulate into zeros, cleared here.
-  if (fresh_sum && out_bytes > 0) PYG_HIP_CHECK(hipMemsetAsync(out, 0, out_bytes, stream));
+  if (fresh_sum && out_bytes > 0)
+    if (int rc = zero_bytes(out, out_bytes, stream)) return rc;
   const bool cas = f.cas || float_atomic_mode() == 1;
   if (op == OP_SUM && (dtype == PYG_F32 || dtype == PYG_F64 || dtype == PYG_BF16 || dtype == PYG_F16))
     note_accumulate("pyg_hip_scatter (sum, atomic kernels)", out, out_bytes,
-                    fresh_sum ? "this call (hipMemsetAsync on the call's stream)" : "the caller (`out=` accumulation)", stream, cas ? 1 : 0);
+                    fresh_sum ? "this call (zero_bytes_kernel on the call's stream)" : "the caller (`out=` accumulation)", stream, cas ? 1 : 0);
   PYG_DISPATCH_ALL(dtype, (run_atomic<scalar_t>(route, op, cas, src, index, out, arg, init, s, stream)));
 }
 
@@ -760,7 +784,7 @@ int pyg_hip_scatter(int op, int dtype, const void* src, const int64_t* index, in
   PYG_HIP_REQUIRE(B >= 0 && E >= 0 && K >= 0 && N >= 0, "scatter: negative size");
   if (B * E * K == 0) {
     if (op == OP_SUM && (index_sorted & PYG_HIP_SCATTER_FRESH_SUM) && out && B * N * K > 0)
-      PYG_HIP_CHECK(hipMemsetAsync(out, 0, dtype_size(dtype) * (size_t)(B * N * K), stream));
+      if (int rc = zero_bytes(out, dtype_size(dtype) * (size_t)(B * N * K), stream)) return rc;
     if ((op == OP_MIN || op == OP_MAX) && arg_out && B * N * K > 0) {
       hipLaunchKernelGGL(fill_i64_kernel, dim3((unsigned)((B * N * K + 255) / 256)), dim3(256), 0, stream,
                          arg_out, B * N * K, E);

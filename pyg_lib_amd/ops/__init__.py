@@ -27,6 +27,11 @@ def segment_matmul(
     ``inputs`` is ``[N, K]`` on a HIP device, ``ptr`` the ``B + 1`` row boundaries (host or device; neither
     placement synchronises), ``other`` ``[B, K, M]``, ``bias`` optionally ``[B, M]``.  Returns ``[N, M]``.
     Differentiable in ``inputs``, ``other`` and ``bias``.
+
+    HIP graphs: with ``ptr`` ON THE DEVICE the call -- forward and backward, with or without ``bias`` -- makes no host read
+    and can be captured (``torch.cuda.graph``) and replayed on new ``inputs`` / ``other`` / ``bias`` AND new contents of
+    ``ptr``.  A ``ptr`` on the host is staged through pinned memory that later calls reuse: such a call must NOT be captured
+    (a replay would copy whatever the pinned slot holds by then; nothing refuses it yet) -- keep ``ptr`` on the device.
     """
     needs_grad = torch.is_grad_enabled() and (inputs.requires_grad or other.requires_grad or
                                               (bias is not None and bias.requires_grad))
@@ -34,7 +39,13 @@ def segment_matmul(
         # bias as a fused GEMM epilogue (the reference: B python-side slice adds, :169-171)
         return torch.ops.pyg.segment_matmul_bias(inputs, ptr, other, bias)
     out = torch.ops.pyg.segment_matmul(inputs, ptr, other)
-    if bias is not None:
+    if bias is not None and ptr.is_cuda:
+        # row r of the bias to the rows ptr[r] .. ptr[r + 1] on the device (slicing by a device `ptr` would read every
+        # boundary back: B synchronisations, and nothing a graph could hold); the same single rounding per element, and
+        # rows behind ptr[B] get no bias
+        rows = gather_csr(bias.to(out.dtype), ptr, out=torch.zeros_like(out))
+        out = out + rows
+    elif bias is not None:
         for i in range(ptr.numel() - 1):
             out[ptr[i]:ptr[i + 1]] += bias[i]
     return out
@@ -80,6 +91,10 @@ def grouped_matmul(
     """``outs[i] = inputs[i] @ others[i] (+ biases[i])`` for lists of independent 2-D operands
     (``[N_i, K_i]`` x ``[K_i, M_i]``) in one launch (interface of the reference's
     ``pyg_lib.ops.grouped_matmul``, pyg_lib/ops/__init__.py:99-134).  Differentiable.
+
+    The group descriptors are planned on the host and staged through pinned memory that later calls reuse.  The call does
+    not synchronise, but it must NOT be captured into a HIP graph: a replay would copy whatever the pinned slot holds by
+    then (nothing refuses it yet).  Call it outside the capture, or use :func:`segment_matmul` with ``ptr`` on the device.
     """
     needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in list(inputs) + list(others))
     if needs_grad:
