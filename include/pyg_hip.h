@@ -57,6 +57,8 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  18: pyg_hip_csr_route, pyg_hip_csr_last_route (which kernels serve a CSR reduction, gather or softmax: asked without
+ *      running, told after).
  *  17: pyg_hip_graclus / _graclus_route / _graclus_last_route / _graclus_tile / _graclus_workspace_size / _graclus_pending_error
  *      (greedy graph matching in parallel rounds).
  *  16: pyg_hip_spline_basis / _basis_backward / _weighting / _weighting_backward_x / _weighting_backward_weight /
@@ -81,7 +83,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 17
+#define PYG_HIP_ABI_VERSION 18
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -1286,6 +1288,45 @@ PYG_HIP_API int pyg_hip_softmax_csr(int dtype, const void* src, const int64_t* p
 PYG_HIP_API int pyg_hip_softmax_csr_backward(int dtype, const void* out, const void* out_grad,
                                              const int64_t* ptr, void* in_grad, int64_t outer, int64_t D,
                                              int64_t inner, int64_t groups, void* stream);
+
+/*
+ * What a CSR call is made of -- segment_csr, gather_csr, softmax_csr and its backward, and the rows back end of pyg_hip_scatter
+ * (csr_rows / sort_rows) and of the COO operators.  pyg_hip_csr_route asks, pyg_hip_csr_last_route tells, as
+ *   '<segment|gather|softmax|softmax_bwd> <kernel> v<V> <none|long|chunks|chunks+combine>[ ch<CH>]'
+ * or 'none' (an empty call: leading x rows x K == 0, for gather and softmax also E == 0) or 'unsupported' (integer mean, softmax
+ * of a dtype other than float32 / float64, an unknown family or dtype, a negative size).
+ *   family   0 ... 3 the reductions, 4 gather_csr, 5 / 6 softmax_csr / its backward with leading = outer, rows = groups, E = D,
+ *            K = inner
+ *   flags    bit 0: the rows are read through a permutation (the sort-based scatter)
+ *   misalign bits 0 ... 3: the low four bits of (src | out); bits 8 ... 15: the low eight bits of the scratch's address
+ *   num_cus  compute units of the device; 0: the current device's.  With num_cus > 0 the query needs no device.
+ * With avg = leading x E / (leading x rows) positions per row and rows of K x sizeof(dtype) bytes:
+ *   V        16 / sizeof(dtype) when rows are whole 16-byte slices and src and out are 16-byte aligned (never softmax, never
+ *            the stream kernel), else 1: elements per thread.  items = leading x rows x K / V.
+ *   kernel   the first line that applies
+ *     stream   rows of at most 16 elements and less than 64 bytes, 12 <= avg < 64, V == 1; not gather, not through a
+ *              permutation; softmax: rows of less than 32 bytes and avg >= 33 (backward: 12).  LDS-streamed, a thread per
+ *              (row, element)
+ *     lanes64  rows of less than 64 bytes, avg >= 256                     64 lanes over the positions of an item
+ *     lanes8   rows of less than 64 bytes, avg >= 64                      8 lanes
+ *     narrow8  rows of 16, 32 or 48 bytes, avg >= 16                      8 lanes
+ *     lanes64  avg >= 1024 and items x 8 < num_cus x 2048
+ *     lanes8   avg >= 64 and items < num_cus x 2048
+ *     narrow8  gather only: rows of less than 64 bytes, avg >= 8 (V > 1) or avg >= 32 (V == 1)
+ *     row1     everything else: one lane per item, the reference's order of operations
+ *   hub rows rows of more than cut = 512 x lanes positions (stream: 4096) are skipped by the row kernel.  None can exist when
+ *            E <= cut or there is one row (softmax: one group) only: 'none'.  Else
+ *     long            no scratch, scratch too small, softmax: a second launch gives every hub row to one workgroup
+ *     chunks          scratch (pyg_hip_csr_hub_workspace_size; from its first 256-byte boundary on): hub rows are registered
+ *                     in chunks of CH = 2048 positions -- doubled until the partial results fit the scratch -- that a second
+ *                     launch deals to all workgroups.  gather, and reductions with E <= CH (every hub is one chunk)
+ *     chunks+combine  reductions with E > CH: a third launch combines the chunks' partial results of a row in chunk order
+ * pyg_hip_csr_route launches nothing and returns a string of the calling thread's that the next query overwrites;
+ * pyg_hip_csr_last_route names the last CSR launch made on the calling thread ('none' before the first).
+ */
+PYG_HIP_API const char* pyg_hip_csr_route(int family, int dtype, int64_t leading, int64_t rows, int64_t E, int64_t K,
+                                          int flags, size_t workspace_bytes, unsigned misalign, int num_cus);
+PYG_HIP_API const char* pyg_hip_csr_last_route(void);
 
 /*
  * Device hash map key -> first position: the kernels behind torch.classes.pyg.CUDAHashMap

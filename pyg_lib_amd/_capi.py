@@ -12,7 +12,7 @@ _HERE = osp.dirname(osp.abspath(__file__))
 _LIB = None
 
 OK = 0
-ABI_VERSION = 17  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
+ABI_VERSION = 18  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
 DTYPES = {
     torch.float32: 0,
     torch.float64: 1,
@@ -59,6 +59,10 @@ def lib() -> ctypes.CDLL:
         L.pyg_hip_matmul_workspace_size.argtypes = [c.c_int64]
         L.pyg_hip_matmul_last_variant.restype = c.c_char_p
         L.pyg_hip_scatter_last_route.restype = c.c_char_p
+        # (family, dtype, leading, rows, E, K, flags, workspace_bytes, misalign, num_cus)
+        L.pyg_hip_csr_route.restype = c.c_char_p
+        L.pyg_hip_csr_route.argtypes = [c.c_int, c.c_int] + [c.c_int64] * 4 + [c.c_int, c.c_size_t, c.c_uint, c.c_int]
+        L.pyg_hip_csr_last_route.restype = c.c_char_p
         L.pyg_hip_segment_matmul.restype = c.c_int
         L.pyg_hip_segment_matmul.argtypes = [c.c_int, c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p,
                                              c.c_void_p, c.c_int64, c.c_int64, c.c_int64, c.c_int64, c.c_void_p,

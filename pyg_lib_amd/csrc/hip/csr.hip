@@ -943,95 +943,55 @@ __global__ __launch_bounds__(256) void softmax_csr_stream_kernel(const T* __rest
   }
 }
 
-// The launches around a row kernel that skips hub rows: hub_begin() in front of it (cut, scratch layout, counters), then the
-// row kernel with st.sc / st.hw, then hub_end().
+// ---- host side: one pure plan per call, one stage that launches it ------------------------------------------------------------
 // (the counters are cleared by a kernel, not by hipMemsetAsync: a 16-byte memset node between kernel nodes is what faulted on the
 // first replay of a captured fused_scatter_reduce, DESIGN.md "HIP graphs")
 __global__ void hub_clear_kernel(int* __restrict__ counters) {
   if (threadIdx.x < 4) counters[threadIdx.x] = 0;
 }
-inline int hub_clear(const HubWs& hw, hipStream_t stream) {
-  hipLaunchKernelGGL(hub_clear_kernel, dim3(1), dim3(64), 0, stream, hw.counters);
-  PYG_HIP_CHECK(hipGetLastError());
-  return PYG_HIP_OK;
-}
 
-struct HubStage {
-  CsrShape sc;
-  HubWs hw;
-  int64_t max_chunks = 0, max_hubs = 0;
-  bool hubs = false;
+// The families of a plan: the four reductions (CSR_SUM ... CSR_MAX), then
+enum { CSR_GATHER = 4, CSR_SOFTMAX = 5, CSR_SOFTMAX_BWD = 6 };
+enum class HubMode { kNone, kLong, kChunks, kChunksCombine };
+
+// what the choice needs to know of an element type
+struct CsrType {
+  int size, acc_size;
+  bool integral, softmax;   // softmax: float32 / float64
 };
-template <typename T, int OP>
-int hub_begin(const CsrShape& s, int64_t cut, HubStage& st, hipStream_t stream) {
-  using acc_t = typename Math<T>::acc_t;
-  st.sc = s;
-  st.sc.hub_ws = nullptr, st.sc.hub_ws_bytes = 0;
-  st.hubs = s.E > cut && s.leading * s.rows > 1;   // (else no row can be that long: nothing is launched for them)
-  if (!st.hubs) return PYG_HIP_OK;
-  st.sc.long_cut = cut;
-  if (hub_plan(s.hub_ws, s.hub_ws_bytes, s.leading * s.E, s.K, sizeof(acc_t), OP == CSR_MIN || OP == CSR_MAX, &st.hw, &st.max_chunks))
-    if (int rc_ = hub_clear(st.hw, stream)) return rc_;
-  st.max_hubs = s.leading * s.E / cut;   // every hub is longer than the cut
-  return PYG_HIP_OK;
+template <typename T>
+constexpr CsrType csr_type() {
+  return {(int)sizeof(T), (int)sizeof(typename Math<T>::acc_t), std::is_integral<T>::value,
+          std::is_same<T, float>::value || std::is_same<T, double>::value};
 }
-template <typename T, int OP, int V, bool PERM>
-int hub_end(const T* sp, const int64_t* indptr, const int64_t* perm, T* op, int64_t* arg, int fresh, const HubStage& st,
-            hipStream_t stream) {
-  if (!st.hubs) return PYG_HIP_OK;
-  if (st.hw.counters) {
-    const int64_t grid = std::min<int64_t>(st.max_chunks, (int64_t)device_info().num_cus * 8);
-    hipLaunchKernelGGL((segment_csr_hub_chunk_kernel<T, OP, V, PERM>), dim3((unsigned)grid), dim3(256), 0, stream, sp, indptr, perm,
-                       op, arg, fresh, st.sc, st.hw);
-    PYG_HIP_CHECK(hipGetLastError());
-    if (st.sc.E > st.hw.CH) {   // (else every hub is one chunk long)
-      const int64_t cgrid = std::min<int64_t>((st.max_hubs * (st.sc.K / V) + 255) / 256, (int64_t)device_info().num_cus * 4);
-      hipLaunchKernelGGL((segment_csr_hub_combine_kernel<T, OP, V>), dim3((unsigned)cgrid), dim3(256), 0, stream, indptr, op, arg,
-                         fresh, st.sc, st.hw);
-    }
-  } else {
-    const int64_t batches = (st.sc.leading * st.sc.rows + 255) / 256;
-    const int64_t grid = std::min<int64_t>(batches, (int64_t)device_info().num_cus * 8);
-    hipLaunchKernelGGL((segment_csr_long_kernel<T, OP, V, PERM>), dim3((unsigned)grid), dim3(256), 0, stream, sp, indptr, perm, op,
-                       arg, fresh, st.sc);
-  }
-  PYG_HIP_CHECK(hipGetLastError());
-  return PYG_HIP_OK;
-}
+inline int csr_type_of(int dtype, CsrType* t) { PYG_DISPATCH_ALL(dtype, (*t = csr_type<scalar_t>(), PYG_HIP_OK)); }
 
-template <typename T, int OP, int V, bool PERM = false>
-int launch_segment(const void* src, const int64_t* indptr, const int64_t* perm, void* out, int64_t* arg, int fresh,
-                   const CsrShape& s, hipStream_t stream) {
-  const int64_t items = s.leading * s.rows * (s.K / V);
-  const int L = pick_lanes(items, s.leading * s.E, s.leading * s.rows, s.K * (int64_t)sizeof(T));
-  const T* sp = static_cast<const T*>(src);
-  T* op = static_cast<T*>(out);
-  HubStage st;
-  if (int rc_ = hub_begin<T, OP>(s, kHubCut * (int64_t)L, st, stream)) return rc_;
-#define PYG_CSR_LAUNCH(LL)                                                                                   \
-  hipLaunchKernelGGL((segment_csr_kernel<T, OP, V, LL, PERM>), dim3((unsigned)((items * LL + 255) / 256)), dim3(256), \
-                     0, stream, sp, indptr, perm, op, arg, fresh, st.sc, st.hw)
-  if (L == 64) PYG_CSR_LAUNCH(64);
-  else if (L == 8) PYG_CSR_LAUNCH(8);
-  else PYG_CSR_LAUNCH(1);
-#undef PYG_CSR_LAUNCH
-  PYG_HIP_CHECK(hipGetLastError());
-  return hub_end<T, OP, V, PERM>(sp, indptr, perm, op, arg, fresh, st, stream);
-}
+// A call as the choice sees it: plain numbers.  Softmax: leading = outer, rows = groups, E = D, K = inner.
+struct CsrCall {
+  int family;
+  CsrType t;
+  int64_t leading, rows, E, K;
+  bool perm;            // rows are read through a permutation (the sort-based scatter)
+  unsigned misalign;    // low four bits of src | out
+  unsigned ws_low;      // low eight bits of the offered scratch's address ...
+  size_t ws_bytes;      // ... and its size (0: none)
+  int num_cus;
+};
 
-template <typename T, int OP>
-int launch_stream(const void* src, const int64_t* indptr, void* out, int64_t* arg, int fresh, const CsrShape& s,
-                  hipStream_t stream) {
-  const int rpb = 256 / (int)s.K;
-  const int64_t blocks = s.leading * ((s.rows + rpb - 1) / rpb);
-  HubStage st;
-  if (int rc_ = hub_begin<T, OP>(s, kHubCutStream, st, stream)) return rc_;
-  hipLaunchKernelGGL((segment_csr_stream_kernel<T, OP>), dim3((unsigned)blocks), dim3(256), 0, stream,
-                     static_cast<const T*>(src), indptr, static_cast<T*>(out), arg, fresh, st.sc, rpb, st.hw);
-  PYG_HIP_CHECK(hipGetLastError());
-  return hub_end<T, OP, 1, false>(static_cast<const T*>(src), indptr, nullptr, static_cast<T*>(out), arg, fresh, st, stream);
-}
+// What a call is made of: pyg_hip_csr_route answers it, pyg_hip_csr_last_route reports it, the launch code follows it.
+struct CsrPlan {
+  int family = 0;
+  CsrKernel kernel = CsrKernel::kNone;   // kNone: an empty call, or `unsupported`
+  bool unsupported = false;
+  int V = 1, L = 1, rpb = 0;             // elements per thread, lanes per item; stream: rows per workgroup
+  int64_t cut = INT64_MAX;               // rows of more positions are hubs (INT64_MAX: no row can be one)
+  HubMode hub = HubMode::kNone;
+  HubLayout lay;                         // kChunks / kChunksCombine: the scratch, lay.CH positions per chunk
+  int64_t row_grid = 0, long_grid = 0, chunk_grid = 0, combine_grid = 0;
+  size_t ws_need = 0;                    // pyg_hip_csr_hub_workspace_size
+};
 
+// ---- the thresholds of the choice (with kHubCut, kHubCutStream and kNarrowVecLanesAvg of csr_rows.h) -------------------------
 // rows of less than 64 bytes that are not very long on average take the LDS-streamed kernel (a thread walks its row out of LDS:
 // from ~64 positions per row on, lanes over the positions are faster)
 #ifndef PYG_CSR_STREAM_MAX_AVG
@@ -1048,201 +1008,299 @@ constexpr int64_t kStreamMaxRowBytes = PYG_CSR_STREAM_MAX_ROW_BYTES;
 #define PYG_CSR_STREAM_MIN_AVG 12
 #endif
 constexpr int64_t kStreamMinAvg = PYG_CSR_STREAM_MIN_AVG;
-// (`slices16`: the rows are whole 16-byte slices the row kernel can load as such.  Then the row kernel always wins -- fp32
-// K = 8, 2 positions per row, 16 M positions: 0.71 ms streamed, 0.15 direct; 48 per row: 0.22 streamed, 0.14 with one lane per
-// item, 0.095 with eight; `tools/narrow_row_kernels.py`)
-template <typename T>
-bool use_stream(const CsrShape& s, bool slices16 = false) {
-  if (s.K < 1 || s.K > 16 || s.K * (int64_t)sizeof(T) >= kStreamMaxRowBytes) return false;
-  const int64_t units = s.leading * s.rows;
-  if (units <= 0) return false;
-  const int64_t avg = (s.leading * s.E) / units;
-  if (slices16 && (s.K * (int64_t)sizeof(T) >= 32 || avg < 32 || kNarrowVecLanesAvg < 64)) return false;
-  if (avg < kStreamMinAvg) return false;
-  return avg < kStreamMaxAvg && s.leading * ((s.rows + 255) / 256) < (1ll << 31);
+// (rows of whole 16-byte slices the row kernel can load as such: then the row kernel always wins -- fp32 K = 8, 2 positions
+// per row, 16 M positions: 0.71 ms streamed, 0.15 direct; 48 per row: 0.22 streamed, 0.14 with one lane per item, 0.095 with
+// eight; `tools/narrow_row_kernels.py`.  They stream only if narrow8 is pushed out to 64 positions per row, and then from 32
+// positions per row on and below 32 bytes)
+constexpr int64_t kStreamSlicesMaxRowBytes = 32, kStreamSlicesMinAvg = 32;
+// gather, narrow rows: a thread writing its slice of position after position leaves 16 bytes per row and store instruction;
+// with 8 lanes per item a store covers 8 consecutive positions.  Rows of whole 16-byte slices from 8 positions per row on (fp32
+// K = 4, 16 per row, 16 M positions: 0.213 -> 0.092 ms; K = 12, 48 per row: 0.46 -> 0.22), element-wise rows from 32 (K = 1, 48
+// per row: 0.062 -> 0.039; at 16 per row K = 5 loses: 0.154 -> 0.212): `tools/lease/ab_gather_lanes.sh`
+constexpr int64_t kGatherLanesAvgSlices = 8, kGatherLanesAvg = 32;
+// softmax, the LDS-streamed kernel: inner sizes below 32 bytes in groups of 33 ... 63 positions on average (shorter groups stay
+// in the registers of the one-thread-per-head kernel: inner = 1, 16 per group 0.161 -> 0.114 ms).  Shorter groups and wider
+// heads are faster with one thread per head reading global memory (fp32 inner = 8, 2 per group, 8 M positions: 1.32 -> 0.55 ms
+// forward, 1.52 -> 0.39 backward; inner = 1, 2 per group: 0.37 -> 0.14; but inner = 1, 16 per group: 0.16 streamed, 0.35
+// direct; `tools/narrow_softmax_kernels.py`)
+#ifndef PYG_SOFTMAX_STREAM_MIN_AVG
+#define PYG_SOFTMAX_STREAM_MIN_AVG 33
+#endif
+constexpr int64_t kSoftmaxStreamMinAvg = PYG_SOFTMAX_STREAM_MIN_AVG;
+// (backward keeps two values per position: 16 in registers, so the streamed kernel takes over earlier)
+constexpr int64_t kSoftmaxBwdStreamMinAvg = 12;
+constexpr int64_t kSoftmaxStreamMaxRowBytes = 32;
+
+// a call that launches nothing
+inline bool csr_empty(int family, int64_t leading, int64_t rows, int64_t E, int64_t K) {
+  return leading * rows * K == 0 || (family >= CSR_GATHER && E == 0);
 }
 
-template <typename T>
-int run_segment(int op, const void* src, const int64_t* indptr, void* out, int64_t* arg, int fresh, const CsrShape& s,
-                hipStream_t stream) {
-  constexpr int VMAX = 16 / (int)sizeof(T);
-  const bool vec = VMAX > 1 && s.K % VMAX == 0 && ((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0);
-  if (use_stream<T>(s, vec)) {
-    switch (op) {
-      case CSR_SUM: return launch_stream<T, CSR_SUM>(src, indptr, out, arg, fresh, s, stream);
-      case CSR_MEAN:
-        if constexpr (std::is_integral<T>::value) return fail(PYG_HIP_ERR_INVALID, "segment_mean_csr: floating dtypes only");
-        else return launch_stream<T, CSR_MEAN>(src, indptr, out, arg, fresh, s, stream);
-      case CSR_MIN: return launch_stream<T, CSR_MIN>(src, indptr, out, arg, fresh, s, stream);
-      case CSR_MAX: return launch_stream<T, CSR_MAX>(src, indptr, out, arg, fresh, s, stream);
-      default: return fail(PYG_HIP_ERR_INVALID, "segment_csr: unknown reduction %d", op);
+// THE choice: the table of pyg_hip_csr_route in pyg_hip.h.  Pure: no HIP call, no global.
+inline CsrPlan csr_plan(const CsrCall& c) {
+  CsrPlan p;
+  p.family = c.family;
+  const bool gather = c.family == CSR_GATHER, softmax = c.family >= CSR_SOFTMAX;
+  if (c.family < 0 || c.family > CSR_SOFTMAX_BWD) return p.unsupported = true, p;
+  const bool minmax = c.family == CSR_MIN || c.family == CSR_MAX;
+  const size_t acc_bytes = gather ? 0 : (size_t)c.t.acc_size;   // (gather keeps no partial results)
+  if (HubLayout need; !softmax && c.K > 0 && hub_layout(c.leading * c.E, c.K, acc_bytes, minmax, true, 0, 0, &need))
+    p.ws_need = need.bytes + 256;   // + alignment slack
+  if (csr_empty(c.family, c.leading, c.rows, c.E, c.K)) return p;
+  if ((c.family == CSR_MEAN && c.t.integral) || (softmax && !c.t.softmax)) return p.unsupported = true, p;
+
+  const int64_t units = c.leading * c.rows;   // rows of all slices
+  const int64_t avg = c.leading * c.E / units;
+  const int64_t row_bytes = c.K * c.t.size;
+  const int vmax = 16 / c.t.size;
+  p.V = !softmax && vmax > 1 && c.K % vmax == 0 && c.misalign % 16 == 0 ? vmax : 1;   // 16-byte slices or elements
+  bool stream = !gather && !c.perm && c.K <= 16 && row_bytes < kStreamMaxRowBytes && avg >= kStreamMinAvg && avg < kStreamMaxAvg &&
+                c.leading * ((c.rows + 255) / 256) < (1ll << 31);
+  if (p.V > 1) stream = stream && row_bytes < kStreamSlicesMaxRowBytes && avg >= kStreamSlicesMinAvg && kNarrowVecLanesAvg >= 64;
+  if (softmax)
+    stream = stream && row_bytes < kSoftmaxStreamMaxRowBytes &&
+             avg >= (c.family == CSR_SOFTMAX_BWD ? kSoftmaxBwdStreamMinAvg : kSoftmaxStreamMinAvg);
+  int64_t cut;
+  if (stream) {
+    p.kernel = CsrKernel::kStream, p.V = 1;
+    p.rpb = 256 / (int)c.K;
+    p.row_grid = c.leading * ((c.rows + p.rpb - 1) / p.rpb);
+    cut = kHubCutStream;
+  } else {
+    const int64_t items = units * (c.K / p.V);
+    p.kernel = pick_row_kernel(items, c.leading * c.E, units, c.num_cus, row_bytes);
+    if (gather && p.kernel == CsrKernel::kRow1 && row_bytes < 64 && avg >= (p.V > 1 ? kGatherLanesAvgSlices : kGatherLanesAvg))
+      p.kernel = CsrKernel::kNarrow8;
+    p.L = kernel_lanes(p.kernel);
+    p.row_grid = (items * p.L + 255) / 256;
+    cut = kHubCut * (int64_t)p.L;
+  }
+  // hubs: a group of softmax lies in one slice's ptr, which all slices share
+  const int64_t hub_rows = softmax ? c.rows : units;
+  if (c.E <= cut || hub_rows <= 1) return p;   // no row can be that long: nothing is launched for them
+  p.cut = cut;
+  p.hub = HubMode::kLong;
+  p.long_grid = std::min<int64_t>((hub_rows + 255) / 256, (int64_t)c.num_cus * 8);
+  if (!softmax && hub_layout(c.leading * c.E, c.K, acc_bytes, minmax, false, c.ws_low, c.ws_bytes, &p.lay)) {
+    p.chunk_grid = std::min<int64_t>(p.lay.max_chunks, (int64_t)c.num_cus * 8);
+    if (!gather && c.E > p.lay.CH) {   // (else every hub is one chunk long)
+      p.hub = HubMode::kChunksCombine;
+      const int64_t max_hubs = c.leading * c.E / cut;   // every hub is longer than the cut
+      p.combine_grid = std::min<int64_t>((max_hubs * (c.K / p.V) + 255) / 256, (int64_t)c.num_cus * 4);
+    } else {
+      p.hub = HubMode::kChunks;
     }
   }
-#define PYG_CSR_OP(OPC)                                                                              \
-  return vec ? launch_segment<T, OPC, VMAX>(src, indptr, nullptr, out, arg, fresh, s, stream)        \
-             : launch_segment<T, OPC, 1>(src, indptr, nullptr, out, arg, fresh, s, stream)
+  return p;
+}
+
+// '<segment|gather|softmax|softmax_bwd> <kernel> v<V> <none|long|chunks|chunks+combine>[ ch<CH>]', 'none' or 'unsupported'
+inline void plan_name(const CsrPlan& p, char* buf, size_t n) {
+  static const char* const kKernels[] = {"none", "row1", "narrow8", "lanes8", "lanes64", "stream"};
+  static const char* const kHubs[] = {"none", "long", "chunks", "chunks+combine"};
+  if (p.kernel == CsrKernel::kNone) {
+    snprintf(buf, n, "%s", p.unsupported ? "unsupported" : "none");
+    return;
+  }
+  const char* family = p.family < CSR_GATHER ? "segment" : p.family == CSR_GATHER ? "gather"
+                       : p.family == CSR_SOFTMAX ? "softmax" : "softmax_bwd";
+  const int len = snprintf(buf, n, "%s %s v%d %s", family, kKernels[(int)p.kernel], p.V, kHubs[(int)p.hub]);
+  if (p.hub >= HubMode::kChunks) snprintf(buf + len, n - len, " ch%lld", (long long)p.lay.CH);
+}
+
+// pyg_hip_csr_last_route(): the plan of the last CSR launch on this thread (named when asked for, not on every launch)
+thread_local CsrPlan g_last_plan;
+inline void note_plan(const CsrPlan& p) { g_last_plan = p; }
+inline int note_empty() {
+  note_plan(CsrPlan{});
+  return PYG_HIP_OK;
+}
+// (softmax of a dtype other than float32 / float64: there is no type to plan with)
+inline int softmax_unsupported(const char* op, int dtype) {
+  CsrPlan p;
+  p.unsupported = true;
+  note_plan(p);
+  return fail(PYG_HIP_ERR_INVALID, "%s: float32 / float64 only (dtype %d)", op, dtype);
+}
+
+// the plan of a launch, noted.  `s` carries the caller's scratch; a, b: the two buffers read or written 16 bytes at a time
+template <typename T>
+CsrPlan plan_launch(int family, const CsrShape& s, bool perm, const void* a, const void* b) {
+  const CsrCall c{family, csr_type<T>(), s.leading, s.rows, s.E, s.K, perm,
+                  (unsigned)((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15),
+                  (unsigned)(reinterpret_cast<uintptr_t>(s.hub_ws) & 255), s.hub_ws ? s.hub_ws_bytes : 0, device_info().num_cus};
+  const CsrPlan p = csr_plan(c);
+  note_plan(p);
+  return p;
+}
+
+// the shape as the kernels get it: the plan's cut, no host-side scratch
+inline CsrShape kernel_shape(const CsrShape& s, const CsrPlan& p) {
+  CsrShape sc = s;
+  sc.hub_ws = nullptr, sc.hub_ws_bytes = 0;
+  sc.long_cut = p.cut;
+  return sc;
+}
+inline HubWs plan_scratch(const CsrPlan& p, void* ws) { return p.hub >= HubMode::kChunks ? hub_bind(p.lay, ws) : HubWs{}; }
+
+// f(integral_constant<int, L>) for the plan's lanes per item
+template <typename F>
+void with_lanes(int L, F f) {
+  if (L == 64) f(std::integral_constant<int, 64>{});
+  else if (L == 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 1>{});
+}
+
+// The launches of a plan, for every family: clear the counters of the scratch, run the row kernel -- it skips the hub rows
+// and, with scratch, registers them --, then deal the hubs' chunks to all workgroups and combine their partial results, or,
+// without scratch, find the hubs again and give each to one workgroup (`*_long`).  row() launches the plan's row kernel;
+// chunk / combine / lng launch theirs on the grid they are given.
+template <typename Row, typename Chunk, typename Combine, typename Long>
+int run_plan(const CsrPlan& p, const HubWs& hw, hipStream_t stream, Row row, Chunk chunk, Combine combine, Long lng) {
+  if (p.hub >= HubMode::kChunks) {
+    hipLaunchKernelGGL(hub_clear_kernel, dim3(1), dim3(64), 0, stream, hw.counters);
+    PYG_HIP_CHECK(hipGetLastError());
+  }
+  row();
+  PYG_HIP_CHECK(hipGetLastError());
+  if (p.hub >= HubMode::kChunks) {
+    chunk(dim3((unsigned)p.chunk_grid));
+    PYG_HIP_CHECK(hipGetLastError());
+    if (p.hub == HubMode::kChunksCombine) combine(dim3((unsigned)p.combine_grid));
+  } else if (p.hub == HubMode::kLong) {
+    lng(dim3((unsigned)p.long_grid));
+  }
+  PYG_HIP_CHECK(hipGetLastError());
+  return PYG_HIP_OK;
+}
+
+template <typename T, int OP, bool PERM, int V>
+int launch_segment(const CsrPlan& p, const T* sp, const int64_t* indptr, const int64_t* perm, T* op, int64_t* arg, int fresh,
+                   const CsrShape& s, hipStream_t stream) {
+  const CsrShape sc = kernel_shape(s, p);
+  const HubWs hw = plan_scratch(p, s.hub_ws);
+  const dim3 grid((unsigned)p.row_grid), block(256);
+  return run_plan(
+      p, hw, stream,
+      [&] {
+        if constexpr (!PERM && V == 1) {
+          if (p.kernel == CsrKernel::kStream) {
+            hipLaunchKernelGGL((segment_csr_stream_kernel<T, OP>), grid, block, 0, stream, sp, indptr, op, arg, fresh, sc, p.rpb, hw);
+            return;
+          }
+        }
+        with_lanes(p.L, [&](auto l) {
+          hipLaunchKernelGGL((segment_csr_kernel<T, OP, V, decltype(l)::value, PERM>), grid, block, 0, stream, sp, indptr, perm, op,
+                             arg, fresh, sc, hw);
+        });
+      },
+      [&](dim3 g) {
+        hipLaunchKernelGGL((segment_csr_hub_chunk_kernel<T, OP, V, PERM>), g, block, 0, stream, sp, indptr, perm, op, arg, fresh, sc, hw);
+      },
+      [&](dim3 g) {
+        hipLaunchKernelGGL((segment_csr_hub_combine_kernel<T, OP, V>), g, block, 0, stream, indptr, op, arg, fresh, sc, hw);
+      },
+      [&](dim3 g) {
+        hipLaunchKernelGGL((segment_csr_long_kernel<T, OP, V, PERM>), g, block, 0, stream, sp, indptr, perm, op, arg, fresh, sc);
+      });
+}
+
+// a reduction over plain rows (perm == nullptr) or over rows read through perm[] (never streamed, no mean)
+template <typename T>
+int run_segment(int op, const void* src, const int64_t* indptr, const int64_t* perm, void* out, int64_t* arg, int fresh,
+                const CsrShape& s, hipStream_t stream) {
+  constexpr int VMAX = 16 / (int)sizeof(T);
+  const CsrPlan p = plan_launch<T>(op, s, perm != nullptr, src, out);
+  const T* sp = static_cast<const T*>(src);
+  T* dp = static_cast<T*>(out);
+#define PYG_CSR_OP(OPC, PERM)                                                                       \
+  (p.V > 1 ? launch_segment<T, OPC, PERM, VMAX>(p, sp, indptr, perm, dp, arg, fresh, s, stream)     \
+           : launch_segment<T, OPC, PERM, 1>(p, sp, indptr, perm, dp, arg, fresh, s, stream))
   switch (op) {
-    case CSR_SUM: PYG_CSR_OP(CSR_SUM);
+    case CSR_SUM: return perm ? PYG_CSR_OP(CSR_SUM, true) : PYG_CSR_OP(CSR_SUM, false);
     case CSR_MEAN:
       if constexpr (std::is_integral<T>::value) return fail(PYG_HIP_ERR_INVALID, "segment_mean_csr: floating dtypes only");
-      else PYG_CSR_OP(CSR_MEAN);
-    case CSR_MIN: PYG_CSR_OP(CSR_MIN);
-    case CSR_MAX: PYG_CSR_OP(CSR_MAX);
+      else return PYG_CSR_OP(CSR_MEAN, false);
+    case CSR_MIN: return perm ? PYG_CSR_OP(CSR_MIN, true) : PYG_CSR_OP(CSR_MIN, false);
+    case CSR_MAX: return perm ? PYG_CSR_OP(CSR_MAX, true) : PYG_CSR_OP(CSR_MAX, false);
     default: return fail(PYG_HIP_ERR_INVALID, "segment_csr: unknown reduction %d", op);
   }
 #undef PYG_CSR_OP
 }
 
 template <typename T, int V>
-int launch_gather(const void* src, const int64_t* indptr, void* out, const CsrShape& s, hipStream_t stream) {
-  const int64_t items = s.leading * s.rows * (s.K / V);
-  int L = pick_lanes(items, s.leading * s.E, s.leading * s.rows, s.K * (int64_t)sizeof(T));
-  // narrow rows: a thread writing its slice of position after position leaves 16 bytes per row and store instruction; with
-  // 8 lanes per item a store covers 8 consecutive positions.  Rows of whole 16-byte slices from 8 positions per row on (fp32
-  // K = 4, 16 per row, 16 M positions: 0.213 -> 0.092 ms; K = 12, 48 per row: 0.46 -> 0.22), element-wise rows from 32 (K = 1, 48
-  // per row: 0.062 -> 0.039; at 16 per row K = 5 loses: 0.154 -> 0.212): `tools/lease/ab_gather_lanes.sh`
-  if (L == 1 && s.K * (int64_t)sizeof(T) < 64 && s.leading * s.rows > 0 &&
-      (s.leading * s.E) / (s.leading * s.rows) >= (V > 1 ? 8 : 32))
-    L = 8;
-  CsrShape sc = s;
-  sc.hub_ws = nullptr, sc.hub_ws_bytes = 0;
-  const int64_t cut = kHubCut * (int64_t)L;
-  const bool hubs = s.E > cut && s.leading * s.rows > 1;
-  if (hubs) sc.long_cut = cut;
-  HubWs hw;
-  int64_t max_chunks = 0;
-  if (hubs && hub_plan(s.hub_ws, s.hub_ws_bytes, s.leading * s.E, s.K, 0, false, &hw, &max_chunks))
-    if (int rc_ = hub_clear(hw, stream)) return rc_;
-#define PYG_CSR_LAUNCH(LL)                                                                                  \
-  hipLaunchKernelGGL((gather_csr_kernel<T, V, LL>), dim3((unsigned)((items * LL + 255) / 256)), dim3(256), 0, \
-                     stream, static_cast<const T*>(src), indptr, static_cast<T*>(out), sc, hw)
-  if (L == 64) PYG_CSR_LAUNCH(64);
-  else if (L == 8) PYG_CSR_LAUNCH(8);
-  else PYG_CSR_LAUNCH(1);
-#undef PYG_CSR_LAUNCH
-  PYG_HIP_CHECK(hipGetLastError());
-  if (hubs && hw.counters) {
-    const int64_t grid = std::min<int64_t>(max_chunks, (int64_t)device_info().num_cus * 8);
-    hipLaunchKernelGGL((gather_csr_hub_chunk_kernel<T, V>), dim3((unsigned)grid), dim3(256), 0, stream, static_cast<const T*>(src),
-                       indptr, static_cast<T*>(out), sc, hw);
-    PYG_HIP_CHECK(hipGetLastError());
-  } else if (hubs) {
-    const int64_t batches = (s.leading * s.rows + 255) / 256;
-    const int64_t grid = std::min<int64_t>(batches, (int64_t)device_info().num_cus * 8);
-    hipLaunchKernelGGL((gather_csr_long_kernel<T, V>), dim3((unsigned)grid), dim3(256), 0, stream, static_cast<const T*>(src),
-                       indptr, static_cast<T*>(out), sc);
-    PYG_HIP_CHECK(hipGetLastError());
-  }
-  return PYG_HIP_OK;
+int launch_gather(const CsrPlan& p, const T* sp, const int64_t* indptr, T* op, const CsrShape& s, hipStream_t stream) {
+  const CsrShape sc = kernel_shape(s, p);
+  const HubWs hw = plan_scratch(p, s.hub_ws);
+  const dim3 grid((unsigned)p.row_grid), block(256);
+  return run_plan(
+      p, hw, stream,
+      [&] {
+        with_lanes(p.L, [&](auto l) {
+          hipLaunchKernelGGL((gather_csr_kernel<T, V, decltype(l)::value>), grid, block, 0, stream, sp, indptr, op, sc, hw);
+        });
+      },
+      [&](dim3 g) { hipLaunchKernelGGL((gather_csr_hub_chunk_kernel<T, V>), g, block, 0, stream, sp, indptr, op, sc, hw); },
+      [](dim3) {},   // (no partial results)
+      [&](dim3 g) { hipLaunchKernelGGL((gather_csr_long_kernel<T, V>), g, block, 0, stream, sp, indptr, op, sc); });
 }
 
 template <typename T>
 int run_gather_csr(const void* src, const int64_t* indptr, void* out, const CsrShape& s, hipStream_t stream) {
   constexpr int VMAX = 16 / (int)sizeof(T);
-  const bool vec = VMAX > 1 && s.K % VMAX == 0 && ((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0);
-  return vec ? launch_gather<T, VMAX>(src, indptr, out, s, stream) : launch_gather<T, 1>(src, indptr, out, s, stream);
+  const CsrPlan p = plan_launch<T>(CSR_GATHER, s, false, src, out);
+  const T* sp = static_cast<const T*>(src);
+  T* op = static_cast<T*>(out);
+  return p.V > 1 ? launch_gather<T, VMAX>(p, sp, indptr, op, s, stream) : launch_gather<T, 1>(p, sp, indptr, op, s, stream);
 }
 
 template <typename T, bool BACKWARD>
-int launch_softmax_long(const void* x, const void* dy, const int64_t* ptr, void* y, int64_t outer, int64_t D, int64_t inner,
-                        int64_t groups, int64_t cut, hipStream_t stream) {
-  const int64_t grid = std::min<int64_t>((groups + 255) / 256, (int64_t)device_info().num_cus * 8);
-  hipLaunchKernelGGL((softmax_csr_long_kernel<T, BACKWARD>), dim3((unsigned)grid), dim3(256), 0, stream, static_cast<const T*>(x),
-                     static_cast<const T*>(dy), ptr, static_cast<T*>(y), outer, D, inner, groups, cut);
-  PYG_HIP_CHECK(hipGetLastError());
-  return PYG_HIP_OK;
-}
-
-template <typename T, bool BACKWARD>
-int run_softmax(const void* x, const void* dy, const int64_t* ptr, void* y, int64_t outer, int64_t D, int64_t inner,
+int run_softmax(const void* x_, const void* dy_, const int64_t* ptr, void* y_, int64_t outer, int64_t D, int64_t inner,
                 int64_t groups, hipStream_t stream) {
-  {
-    const CsrShape s{outer, groups, D, inner, 0};
-    // the LDS-streamed kernel: inner sizes below 32 bytes in groups of 33 ... 63 positions on average (shorter groups stay in
-    // the registers of the one-thread-per-head kernel: inner = 1, 16 per group 0.161 -> 0.114 ms).  Shorter groups and
-    // wider heads are faster with one thread per head reading global memory (fp32 inner = 8, 2 per group, 8 M positions: 1.32 ->
-    // 0.55 ms forward, 1.52 -> 0.39 backward; inner = 1, 2 per group: 0.37 -> 0.14; but inner = 1, 16 per group: 0.16 streamed,
-    // 0.35 direct; `tools/narrow_softmax_kernels.py`)
-#ifndef PYG_SOFTMAX_STREAM_MIN_AVG
-#define PYG_SOFTMAX_STREAM_MIN_AVG 33
-#endif
-    // (backward keeps two values per position: 16 in registers, so the streamed kernel takes over earlier)
-    constexpr int64_t kMinAvg = BACKWARD ? 12 : PYG_SOFTMAX_STREAM_MIN_AVG;
-    if (use_stream<T>(s) && inner * (int64_t)sizeof(T) < 32 && D * outer >= kMinAvg * groups * outer) {
-      const int rpb = 256 / (int)inner;
-      const int64_t blocks = outer * ((groups + rpb - 1) / rpb);
-      const int lds = (int)(sizeof(T) * softmax_values<T, BACKWARD>() * (BACKWARD ? 2 : 1));
-      if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&softmax_csr_stream_kernel<T, BACKWARD>), lds)) return rc_;
-      CsrShape sc = s;
-      const bool hubs = D > kHubCutStream && groups > 1;
-      if (hubs) sc.long_cut = kHubCutStream;
-      hipLaunchKernelGGL((softmax_csr_stream_kernel<T, BACKWARD>), dim3((unsigned)blocks), dim3(256), lds, stream,
-                         static_cast<const T*>(x), static_cast<const T*>(dy), ptr, static_cast<T*>(y), sc, rpb);
-      PYG_HIP_CHECK(hipGetLastError());
-      return hubs ? launch_softmax_long<T, BACKWARD>(x, dy, ptr, y, outer, D, inner, groups, kHubCutStream, stream) : PYG_HIP_OK;
-    }
-  }
-  const int64_t items = groups * outer * inner;
-  const int L = pick_lanes(items, D * outer * inner, items, inner * (int64_t)sizeof(T));
-  const int64_t cut = kHubCut * (int64_t)L;
-  const bool hubs = D > cut && groups > 1;
-  const int64_t long_cut = hubs ? cut : INT64_MAX;
-#define PYG_SM_LAUNCH(LL)                                                                                         \
-  hipLaunchKernelGGL((softmax_csr_kernel<T, LL, BACKWARD>), dim3((unsigned)((items * LL + 255) / 256)), dim3(256), \
-                     0, stream, static_cast<const T*>(x), static_cast<const T*>(dy), ptr, static_cast<T*>(y), outer, \
-                     D, inner, groups, long_cut)
-  if (L == 64) PYG_SM_LAUNCH(64);
-  else if (L == 8) PYG_SM_LAUNCH(8);
-  else PYG_SM_LAUNCH(1);
-#undef PYG_SM_LAUNCH
-  PYG_HIP_CHECK(hipGetLastError());
-  return hubs ? launch_softmax_long<T, BACKWARD>(x, dy, ptr, y, outer, D, inner, groups, cut, stream) : PYG_HIP_OK;
-}
-
-template <typename T>
-int run_minmax_perm(int is_min, const void* src, const int64_t* indptr, const int64_t* perm, void* out, int64_t* arg,
-                    int fresh, const CsrShape& s, hipStream_t stream) {
-  constexpr int VMAX = 16 / (int)sizeof(T);
-  const bool vec = VMAX > 1 && s.K % VMAX == 0 && ((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0);
-#define PYG_MM(OPC, VV)                                                                                  \
-  (perm ? launch_segment<T, OPC, VV, true>(src, indptr, perm, out, arg, fresh, s, stream)                \
-        : launch_segment<T, OPC, VV, false>(src, indptr, nullptr, out, arg, fresh, s, stream))
-  if (is_min) return vec ? PYG_MM(CSR_MIN, VMAX) : PYG_MM(CSR_MIN, 1);
-  return vec ? PYG_MM(CSR_MAX, VMAX) : PYG_MM(CSR_MAX, 1);
-#undef PYG_MM
+  const CsrShape s{outer, groups, D, inner, 0};
+  const CsrPlan p = plan_launch<T>(BACKWARD ? CSR_SOFTMAX_BWD : CSR_SOFTMAX, s, false, nullptr, nullptr);
+  const T *x = static_cast<const T*>(x_), *dy = static_cast<const T*>(dy_);
+  T* y = static_cast<T*>(y_);
+  const int lds = (int)(sizeof(T) * softmax_values<T, BACKWARD>() * (BACKWARD ? 2 : 1));
+  if (p.kernel == CsrKernel::kStream)
+    if (int rc_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&softmax_csr_stream_kernel<T, BACKWARD>), lds)) return rc_;
+  const dim3 grid((unsigned)p.row_grid), block(256);
+  return run_plan(
+      p, HubWs{}, stream,
+      [&] {
+        if (p.kernel == CsrKernel::kStream) {
+          hipLaunchKernelGGL((softmax_csr_stream_kernel<T, BACKWARD>), grid, block, lds, stream, x, dy, ptr, y, kernel_shape(s, p), p.rpb);
+          return;
+        }
+        with_lanes(p.L, [&](auto l) {
+          hipLaunchKernelGGL((softmax_csr_kernel<T, decltype(l)::value, BACKWARD>), grid, block, 0, stream, x, dy, ptr, y, outer, D,
+                             inner, groups, p.cut);
+        });
+      },
+      [](dim3) {}, [](dim3) {},   // (no scratch: the hub groups always go to the *_long kernel)
+      [&](dim3 g) {
+        hipLaunchKernelGGL((softmax_csr_long_kernel<T, BACKWARD>), g, block, 0, stream, x, dy, ptr, y, outer, D, inner, groups, p.cut);
+      });
 }
 
 }  // namespace
 
-template <typename T>
-int run_sum_perm(const void* src, const int64_t* indptr, const int64_t* perm, void* out, int fresh, const CsrShape& s,
-                 hipStream_t stream) {
-  constexpr int VMAX = 16 / (int)sizeof(T);
-  const bool vec = VMAX > 1 && s.K % VMAX == 0 && ((uintptr_t)src % 16 == 0) && ((uintptr_t)out % 16 == 0);
-  return vec ? launch_segment<T, CSR_SUM, VMAX, true>(src, indptr, perm, out, nullptr, fresh, s, stream)
-             : launch_segment<T, CSR_SUM, 1, true>(src, indptr, perm, out, nullptr, fresh, s, stream);
-}
-
 int segment_csr_sum(int dtype, const void* src, const int64_t* indptr, int64_t indptr_stride, const int64_t* perm, void* out,
                     int64_t leading, int64_t rows, int64_t E, int64_t K, int fresh, hipStream_t stream, void* hub_ws,
                     size_t hub_ws_bytes) {
-  if (leading * rows * K == 0) return PYG_HIP_OK;
+  if (csr_empty(CSR_SUM, leading, rows, E, K)) return note_empty();
   CsrShape s{leading, rows, E, K, indptr_stride};
   s.hub_ws = hub_ws, s.hub_ws_bytes = hub_ws_bytes;
-  if (perm) PYG_DISPATCH_ALL(dtype, (run_sum_perm<scalar_t>(src, indptr, perm, out, fresh, s, stream)));
-  PYG_DISPATCH_ALL(dtype, (run_segment<scalar_t>(CSR_SUM, src, indptr, out, nullptr, fresh, s, stream)));
+  PYG_DISPATCH_ALL(dtype, (run_segment<scalar_t>(CSR_SUM, src, indptr, perm, out, nullptr, fresh, s, stream)));
 }
 
 int segment_csr_minmax(int is_min, int dtype, const void* src, const int64_t* indptr, int64_t indptr_stride,
                        const int64_t* perm, void* out, int64_t* arg, int fresh, int64_t leading, int64_t rows,
                        int64_t E, int64_t K, hipStream_t stream, void* hub_ws, size_t hub_ws_bytes) {
-  if (leading * rows * K == 0) return PYG_HIP_OK;
+  if (csr_empty(CSR_MIN, leading, rows, E, K)) return note_empty();
   CsrShape s{leading, rows, E, K, indptr_stride};
   s.hub_ws = hub_ws, s.hub_ws_bytes = hub_ws_bytes;
-  if (!perm) {  // plain rows: small K takes the LDS-streamed kernel
-    PYG_DISPATCH_ALL(dtype, (run_segment<scalar_t>(is_min ? CSR_MIN : CSR_MAX, src, indptr, out, arg, fresh, s, stream)));
-  }
-  PYG_DISPATCH_ALL(dtype, (run_minmax_perm<scalar_t>(is_min, src, indptr, perm, out, arg, fresh, s, stream)));
+  PYG_DISPATCH_ALL(dtype, (run_segment<scalar_t>(is_min ? CSR_MIN : CSR_MAX, src, indptr, perm, out, arg, fresh, s, stream)));
 }
 
 }  // namespace pyg_hip
@@ -1251,18 +1309,31 @@ using namespace pyg_hip;
 
 extern "C" {
 
-size_t pyg_hip_csr_hub_workspace_size(int op, int dtype, int64_t leading, int64_t E, int64_t K) {
-  if (leading < 0 || E < 0 || K <= 0 || op < 0 || op > 4) return 0;
-  size_t acc = 0;
-  switch (dtype) {
-    case PYG_F16: case PYG_BF16: case PYG_F32: case PYG_I32: acc = 4; break;
-    case PYG_F64: case PYG_I64: acc = 8; break;
-    case PYG_I16: acc = 2; break;
-    default: acc = 1; break;
+const char* pyg_hip_csr_route(int family, int dtype, int64_t leading, int64_t rows, int64_t E, int64_t K, int flags,
+                              size_t workspace_bytes, unsigned misalign, int num_cus) {
+  thread_local char name[64];
+  CsrCall c{family, {}, leading, rows, E, K, (flags & 1) != 0, misalign & 15, (misalign >> 8) & 255, workspace_bytes, num_cus};
+  CsrPlan p;
+  if (leading < 0 || rows < 0 || E < 0 || K < 0 || num_cus < 0 || csr_type_of(dtype, &c.t) != PYG_HIP_OK) {
+    p.unsupported = true;
+  } else {
+    if (num_cus == 0) c.num_cus = device_info().num_cus;
+    p = csr_plan(c);
   }
-  const bool gather = op == 4;
-  return hub_plan(nullptr, 0, leading * E, K, gather ? 0 : acc, op == CSR_MIN || op == CSR_MAX, nullptr, nullptr) +
-         (leading * E > kHubCut ? 256 : 0);   // + alignment slack
+  plan_name(p, name, sizeof(name));
+  return name;
+}
+
+const char* pyg_hip_csr_last_route(void) {
+  thread_local char name[64];
+  plan_name(g_last_plan, name, sizeof(name));
+  return name;
+}
+
+size_t pyg_hip_csr_hub_workspace_size(int op, int dtype, int64_t leading, int64_t E, int64_t K) {
+  CsrCall c{op, {}, leading, 0, E, K, false, 0, 0, 0, 0};
+  if (leading < 0 || E < 0 || K <= 0 || op < 0 || op > CSR_GATHER || csr_type_of(dtype, &c.t) != PYG_HIP_OK) return 0;
+  return csr_plan(c).ws_need;
 }
 
 int pyg_hip_segment_csr_ws(int op, int dtype, const void* src, const int64_t* indptr, int64_t indptr_slice_stride,
@@ -1270,13 +1341,14 @@ int pyg_hip_segment_csr_ws(int op, int dtype, const void* src, const int64_t* in
                            void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   PYG_HIP_REQUIRE(leading >= 0 && rows >= 0 && E >= 0 && K >= 0, "segment_csr: negative size");
-  if (leading * rows * K == 0) return PYG_HIP_OK;
+  if (csr_empty(CSR_SUM, leading, rows, E, K)) return note_empty();
+  PYG_HIP_REQUIRE(op >= CSR_SUM && op <= CSR_MAX, "segment_csr: unknown reduction %d", op);
   PYG_HIP_REQUIRE(indptr && out && (src || E == 0), "segment_csr: NULL tensor");
   PYG_HIP_REQUIRE((op != CSR_MIN && op != CSR_MAX) || arg_out, "segment_csr: min/max need arg_out");
   PYG_HIP_REQUIRE(indptr_slice_stride == 0 || indptr_slice_stride >= rows + 1, "segment_csr: bad indptr stride");
   CsrShape s{leading, rows, E, K, indptr_slice_stride};
   s.hub_ws = workspace, s.hub_ws_bytes = workspace ? workspace_bytes : 0;
-  PYG_DISPATCH_ALL(dtype, (run_segment<scalar_t>(op, src, indptr, out, arg_out, fresh, s, stream)));
+  PYG_DISPATCH_ALL(dtype, (run_segment<scalar_t>(op, src, indptr, nullptr, out, arg_out, fresh, s, stream)));
 }
 
 int pyg_hip_segment_csr(int op, int dtype, const void* src, const int64_t* indptr, int64_t indptr_slice_stride,
@@ -1291,7 +1363,7 @@ int pyg_hip_gather_csr_ws(int dtype, const void* src, const int64_t* indptr, int
                           void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   PYG_HIP_REQUIRE(leading >= 0 && rows >= 0 && E >= 0 && K >= 0, "gather_csr: negative size");
-  if (leading * E * K == 0 || rows == 0) return PYG_HIP_OK;
+  if (csr_empty(CSR_GATHER, leading, rows, E, K)) return note_empty();
   PYG_HIP_REQUIRE(src && indptr && out, "gather_csr: NULL tensor");
   CsrShape s{leading, rows, E, K, indptr_slice_stride};
   s.hub_ws = workspace, s.hub_ws_bytes = workspace ? workspace_bytes : 0;
@@ -1307,22 +1379,22 @@ int pyg_hip_softmax_csr(int dtype, const void* src, const int64_t* ptr, void* ou
                         int64_t inner, int64_t groups, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   PYG_HIP_REQUIRE(outer >= 0 && D >= 0 && inner >= 0 && groups >= 0, "softmax_csr: negative size");
-  if (outer * D * inner == 0 || groups == 0) return PYG_HIP_OK;
+  if (csr_empty(CSR_SOFTMAX, outer, groups, D, inner)) return note_empty();
   PYG_HIP_REQUIRE(src && ptr && out, "softmax_csr: NULL tensor");
   if (dtype == PYG_F32) return run_softmax<float, false>(src, nullptr, ptr, out, outer, D, inner, groups, stream);
   if (dtype == PYG_F64) return run_softmax<double, false>(src, nullptr, ptr, out, outer, D, inner, groups, stream);
-  return fail(PYG_HIP_ERR_INVALID, "softmax_csr: float32 / float64 only (dtype %d)", dtype);
+  return softmax_unsupported("softmax_csr", dtype);
 }
 
 int pyg_hip_softmax_csr_backward(int dtype, const void* out, const void* out_grad, const int64_t* ptr, void* in_grad,
                                  int64_t outer, int64_t D, int64_t inner, int64_t groups, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   PYG_HIP_REQUIRE(outer >= 0 && D >= 0 && inner >= 0 && groups >= 0, "softmax_csr_backward: negative size");
-  if (outer * D * inner == 0 || groups == 0) return PYG_HIP_OK;
+  if (csr_empty(CSR_SOFTMAX_BWD, outer, groups, D, inner)) return note_empty();
   PYG_HIP_REQUIRE(out && out_grad && ptr && in_grad, "softmax_csr_backward: NULL tensor");
   if (dtype == PYG_F32) return run_softmax<float, true>(out, out_grad, ptr, in_grad, outer, D, inner, groups, stream);
   if (dtype == PYG_F64) return run_softmax<double, true>(out, out_grad, ptr, in_grad, outer, D, inner, groups, stream);
-  return fail(PYG_HIP_ERR_INVALID, "softmax_csr_backward: float32 / float64 only (dtype %d)", dtype);
+  return softmax_unsupported("softmax_csr_backward", dtype);
 }
 
 }  // extern "C"

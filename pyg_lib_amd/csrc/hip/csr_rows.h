@@ -1,5 +1,5 @@
 // What the CSR-row kernel families share (csr.hip, fused_reduce.hip): the 16-byte pack, pin_all, the accumulator identities
-// and shuffles, the scratch of the hub rows (registration, layout) and the choice of lanes per row.
+// and shuffles, the scratch of the hub rows (registration, layout) and the choice of the row kernel (lanes per row).
 #pragma once
 
 #include "common.h"
@@ -153,41 +153,66 @@ constexpr int64_t kHubChunk = 2048;   // positions per chunk (doubled until the 
 
 inline size_t hub_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// Where the parts of the hub scratch lie: offsets from the first 256-byte boundary of the scratch (`skew` bytes in).
+struct HubLayout {
+  size_t skew = 0, o_hubs = 0, o_chunks = 0, o_part = 0, o_best = 0;
+  size_t bytes = 0;   // all of it, the skew included
+  int64_t CH = 0, max_hubs = 0, max_chunks = 0, max_slots = 0;
+};
+
 // Lays the hub scratch out for `total` positions in rows of K values.  More than total / kHubCut hubs cannot exist; a hub
-// of one chunk needs no slot, a longer one at most 2 * len / CH of them.  Returns the bytes used (0: disabled).
-inline size_t hub_plan(void* ws, size_t ws_bytes, int64_t total, int64_t K, size_t acc_bytes, bool minmax, HubWs* hw,
-                       int64_t* max_chunks_out) {
-  if (total <= kHubCut) return 0;
-  const int64_t max_hubs = total / kHubCut + 1;
+// of one chunk needs no slot, a longer one at most 2 * len / CH of them.  `sizing`: the layout of the smallest chunk length,
+// whatever is offered; else the first chunk length that fits `ws_bytes` bytes at an address whose low eight bits are `ws_low`.
+// False: disabled (no row can be a hub, or nothing fits).
+inline bool hub_layout(int64_t total, int64_t K, size_t acc_bytes, bool minmax, bool sizing, unsigned ws_low, size_t ws_bytes,
+                       HubLayout* lay) {
+  if (total <= kHubCut) return false;
+  lay->max_hubs = total / kHubCut + 1;
+  lay->skew = sizing ? 0 : (256 - (ws_low & 255)) & 255;
   for (int64_t CH = kHubChunk; CH <= (1ll << 22); CH <<= 1) {
-    const int64_t max_chunks = total / CH + max_hubs + 1;
-    const int64_t max_slots = acc_bytes ? 2 * (total / CH) + 2 : 0;
-    const size_t o_hubs = 256;
-    const size_t o_chunks = o_hubs + hub_align(sizeof(HubRec) * (size_t)max_hubs);
-    const size_t o_part = o_chunks + hub_align(sizeof(int2) * (size_t)max_chunks);
-    const size_t o_best = o_part + hub_align(acc_bytes * (size_t)max_slots * (size_t)K);
-    const size_t end = o_best + (minmax ? hub_align(sizeof(int64_t) * (size_t)max_slots * (size_t)K) : 0);
-    if (!hw) return end;   // sizing: the smallest chunk
-    const size_t skew = (256 - (reinterpret_cast<uintptr_t>(ws) & 255)) & 255;
-    if (ws && ws_bytes >= end + skew) {
-      char* w = static_cast<char*>(ws) + skew;
-      hw->counters = reinterpret_cast<int*>(w);
-      hw->hubs = reinterpret_cast<HubRec*>(w + o_hubs);
-      hw->chunks = reinterpret_cast<int2*>(w + o_chunks);
-      hw->partial = w + o_part;
-      hw->partial_best = reinterpret_cast<int64_t*>(w + o_best);
-      hw->CH = CH;
-      const int64_t cap = 0x7fffffff;
-      hw->max_hubs = (int)std::min(max_hubs, cap), hw->max_chunks = (int)std::min(max_chunks, cap);
-      hw->max_slots = (int)std::min(max_slots, cap);
-      *max_chunks_out = max_chunks;
-      return end + skew;
-    }
+    lay->CH = CH;
+    lay->max_chunks = total / CH + lay->max_hubs + 1;
+    lay->max_slots = acc_bytes ? 2 * (total / CH) + 2 : 0;
+    lay->o_hubs = 256;
+    lay->o_chunks = lay->o_hubs + hub_align(sizeof(HubRec) * (size_t)lay->max_hubs);
+    lay->o_part = lay->o_chunks + hub_align(sizeof(int2) * (size_t)lay->max_chunks);
+    lay->o_best = lay->o_part + hub_align(acc_bytes * (size_t)lay->max_slots * (size_t)K);
+    lay->bytes = lay->o_best + (minmax ? hub_align(sizeof(int64_t) * (size_t)lay->max_slots * (size_t)K) : 0) + lay->skew;
+    if (sizing || (ws_bytes && ws_bytes >= lay->bytes)) return true;
     if (!acc_bytes) break;   // (gather: nothing shrinks with longer chunks but the chunk list)
   }
-  return 0;
+  return false;
 }
 
+// the layout on the scratch it was made for
+inline HubWs hub_bind(const HubLayout& lay, void* ws) {
+  HubWs hw;
+  char* w = static_cast<char*>(ws) + lay.skew;
+  hw.counters = reinterpret_cast<int*>(w);
+  hw.hubs = reinterpret_cast<HubRec*>(w + lay.o_hubs);
+  hw.chunks = reinterpret_cast<int2*>(w + lay.o_chunks);
+  hw.partial = w + lay.o_part;
+  hw.partial_best = reinterpret_cast<int64_t*>(w + lay.o_best);
+  hw.CH = lay.CH;
+  const int64_t cap = 0x7fffffff;
+  hw.max_hubs = (int)std::min(lay.max_hubs, cap), hw.max_chunks = (int)std::min(lay.max_chunks, cap);
+  hw.max_slots = (int)std::min(lay.max_slots, cap);
+  return hw;
+}
+
+// Both at once for a caller that holds the scratch (hw == nullptr: sizing).  Returns the bytes used (0: disabled).
+inline size_t hub_plan(void* ws, size_t ws_bytes, int64_t total, int64_t K, size_t acc_bytes, bool minmax, HubWs* hw,
+                       int64_t* max_chunks_out) {
+  HubLayout lay;
+  if (!hub_layout(total, K, acc_bytes, minmax, !hw, (unsigned)(reinterpret_cast<uintptr_t>(ws) & 255), ws ? ws_bytes : 0, &lay))
+    return 0;
+  if (!hw) return lay.bytes;
+  *hw = hub_bind(lay, ws);
+  *max_chunks_out = lay.max_chunks;
+  return lay.bytes;
+}
+
+// ---- the row kernel of a shape ----------------------------------------------------------------------
 // (narrow rows of whole 16-byte slices: 8 lanes per item from 16 positions per row on -- a load instruction then covers 8
 // consecutive positions of a row: fp32 K = 4, 48 per row: 0.096 (streamed) -> 0.044 ms; bf16 K = 8, 16 per row: 0.103 -> 0.062;
 // from 8 per row on it loses: fp32 K = 12: 0.19 -> 0.27.  `tools/lease/ab_narrow_vec_lanes.sh`)
@@ -195,18 +220,29 @@ inline size_t hub_plan(void* ws, size_t ws_bytes, int64_t total, int64_t K, size
 #define PYG_CSR_NARROW_VEC_LANES_AVG 16
 #endif
 constexpr int64_t kNarrowVecLanesAvg = PYG_CSR_NARROW_VEC_LANES_AVG;
-// lanes per item: long rows + too few items to fill the chip
-inline int pick_lanes(int64_t items, int64_t total_len, int64_t units, int64_t row_bytes = 64) {
-  if (units <= 0 || items <= 0) return 1;
+
+// The kernels a CSR call can take: one lane per item, 8 lanes over the positions of narrow rows, lane-split long rows, or the
+// LDS-streamed kernel (csr.hip only).
+enum class CsrKernel { kNone, kRow1, kNarrow8, kLanes8, kLanes64, kStream };
+inline int kernel_lanes(CsrKernel k) {
+  return k == CsrKernel::kLanes64 ? 64 : (k == CsrKernel::kLanes8 || k == CsrKernel::kNarrow8) ? 8 : 1;
+}
+
+// lanes per item: long rows + too few items to fill the `num_cus` compute units
+inline CsrKernel pick_row_kernel(int64_t items, int64_t total_len, int64_t units, int num_cus, int64_t row_bytes = 64) {
+  if (units <= 0 || items <= 0) return CsrKernel::kRow1;
   const int64_t avg = total_len / units;
   // rows narrower than a cache line that are too long for the LDS-streamed kernels: the lanes of an item read neighbouring
   // positions -- one contiguous piece per trip, whatever the number of items (K = 1, 300 positions per row: 0.168 -> ms)
-  if (row_bytes < 64 && avg >= 64) return avg >= 256 ? 64 : 8;
-  if (row_bytes < 64 && row_bytes % 16 == 0 && avg >= kNarrowVecLanesAvg) return 8;
-  const int64_t chip = (int64_t)device_info().num_cus * 2048;  // resident threads
-  if (avg >= 1024 && items * 8 < chip) return 64;
-  if (avg >= 64 && items < chip) return 8;
-  return 1;
+  if (row_bytes < 64 && avg >= 64) return avg >= 256 ? CsrKernel::kLanes64 : CsrKernel::kLanes8;
+  if (row_bytes < 64 && row_bytes % 16 == 0 && avg >= kNarrowVecLanesAvg) return CsrKernel::kNarrow8;
+  const int64_t chip = (int64_t)num_cus * 2048;  // resident threads
+  if (avg >= 1024 && items * 8 < chip) return CsrKernel::kLanes64;
+  if (avg >= 64 && items < chip) return CsrKernel::kLanes8;
+  return CsrKernel::kRow1;
+}
+inline int pick_lanes(int64_t items, int64_t total_len, int64_t units, int num_cus, int64_t row_bytes = 64) {
+  return kernel_lanes(pick_row_kernel(items, total_len, units, num_cus, row_bytes));
 }
 
 }  // namespace

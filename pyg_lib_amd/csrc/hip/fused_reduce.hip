@@ -478,7 +478,7 @@ int launch_rows(const FusedArgs& a, FusedShape s, hipStream_t stream) {
   const int64_t items = s.N * kv;
   // (pick_lanes' rules for few long rows only: its narrow-row rules split buckets of 16 positions, and a bucket that one lane
   // walks is summed in exactly the sequential order)
-  const int L = pick_lanes(items, s.E, s.N);
+  const int L = pick_lanes(items, s.E, s.N, device_info().num_cus);
   const int64_t cut = kHubCut * (int64_t)L;
   const bool hubs = s.E > cut && s.N > 1;
   HubWs hw;

@@ -456,6 +456,14 @@ def scatter_last_route() -> str:
     return _capi.lib().pyg_hip_scatter_last_route().decode()
 
 
+def csr_last_route() -> str:
+    """What the last CSR launch made FROM THE CALLING THREAD was made of (test/diagnostic hook): the last ``segment_*_csr`` /
+    ``gather_csr`` / ``softmax_csr`` op, or the rows back end of a ``scatter_*`` / ``segment_*_coo`` op that took the
+    ``'csr_rows'`` / ``'sort_rows'`` route -- ``'<segment|gather|softmax|softmax_bwd> <kernel> v<V> <hub mode>[ ch<CH>]'``,
+    ``'none'`` or ``'unsupported'``; the rules are the table of ``pyg_hip_csr_route`` in include/pyg_hip.h."""
+    return _capi.lib().pyg_hip_csr_last_route().decode()
+
+
 def matmul_dw_counters() -> Tuple[int, int]:
     """(specialised, general): calls served by the shape-specialised / the general-shape weight-gradient kernels since the
     library was loaded (process wide -- the backward pass runs on an autograd thread)."""

@@ -6,12 +6,14 @@ import numpy as np
 import torch
 
 
-def _chip():
-    return torch.cuda.get_device_properties(0).multi_processor_count * 2048   # resident threads (pick_lanes)
+def _chip(cus=None):
+    """resident threads (pick_row_kernel) of `cus` compute units; None: the device's"""
+    return (cus or torch.cuda.get_device_properties(0).multi_processor_count) * 2048
 
 
-def csr_path(dtype, K, leading, rows, E, gather=False, perm=False):
-    """The row kernel csr.hip picks for a shape (pick_lanes / use_stream / launch_gather restated; 16-byte aligned buffers):
+def csr_path(dtype, K, leading, rows, E, gather=False, perm=False, cus=None):
+    """The row kernel csr.hip picks for a shape (csr_plan / pick_row_kernel restated; 16-byte aligned buffers; checked against
+    the library by tests/test_csr_route.py):
     'row1' (one lane per item), 'narrow8' (8 lanes over the positions of rows of whole 16-byte slices narrower than 64
     bytes), 'lanes8' / 'lanes64' (lane-split long rows), 'stream' (LDS-streamed; never for rows read through a permutation,
     `perm`: the sort-based scatter).  Returns (path, hub cut)."""
@@ -24,7 +26,7 @@ def csr_path(dtype, K, leading, rows, E, gather=False, perm=False):
     rb = K * size
     if not gather and not perm and 1 <= K <= 16 and rb < 64 and not vec and 12 <= avg < 64:
         return 'stream', 4096
-    chip = _chip()
+    chip = _chip(cus)
     items = units * (K // V)
     if rb < 64 and avg >= 64:
         L, name = (64, 'lanes64') if avg >= 256 else (8, 'lanes8')
@@ -39,6 +41,23 @@ def csr_path(dtype, K, leading, rows, E, gather=False, perm=False):
     if gather and L == 1 and rb < 64 and avg >= (8 if V > 1 else 32):
         L, name = 8, 'narrow8'
     return name, 512 * L
+
+
+def hub_mode(E, cut, rows, with_ws):
+    """How a call with the hub cut `cut` deals with hub rows: 'none' when no row can be one (E <= cut, or one row only --
+    softmax: one group); else 'long' without scratch and 'chunks' with scratch of the full size."""
+    if E <= cut or rows <= 1:
+        return 'none'
+    return 'chunks' if with_ws else 'long'
+
+
+def route_parts(route):
+    """(family, kernel, hub mode) of a pyg_hip_csr_last_route answer, in the words of csr_path / softmax_path / hub_mode:
+    'chunks+combine' counts as 'chunks', and softmax's head kernels go by their lanes."""
+    family, kernel, _, hub = route.split()[:4]
+    if family.startswith('softmax'):
+        kernel = {'row1': 'lanes1', 'narrow8': 'lanes8'}.get(kernel, kernel)
+    return family, kernel, hub.split('+')[0]
 
 
 def _lens(rng, rows, lo, hi, hub=0):
@@ -123,7 +142,7 @@ def scatter_path(dtype, op, flags, with_ws, B, E, K, isk=0, ise=1):
 
 
 # ---- csr.hip: run_softmax restated ---------------------------------------------------------------------------------------------
-def softmax_path(dtype, outer, D, inner, groups, backward=False):
+def softmax_path(dtype, outer, D, inner, groups, backward=False, cus=None):
     """('stream' | 'lanes1' | 'lanes8' | 'lanes64', hub cut): the LDS-streamed kernel, or the head kernel with 1 / 8 / 64 lanes
     per (group, head) -- with one lane, groups of 2 .. 32 positions (backward: 16) stay in registers, in three size classes
     (.. 4, .. 16, .. 32).  Groups longer than the cut go to the hub kernel."""
@@ -137,9 +156,9 @@ def softmax_path(dtype, outer, D, inner, groups, backward=False):
         L = 64 if avg >= 256 else 8
     elif rb < 64 and rb % 16 == 0 and avg >= 16:
         L = 8
-    elif avg >= 1024 and items * 8 < _chip():
+    elif avg >= 1024 and items * 8 < _chip(cus):
         L = 64
-    elif avg >= 64 and items < _chip():
+    elif avg >= 64 and items < _chip(cus):
         L = 8
     else:
         L = 1

@@ -39,7 +39,7 @@ from pyg_lib_amd import ops
 from tests import _capture
 from tests._capture import same_bits
 from tests._guard import guarded
-from tests._paths import CSR_CASES, csr_path, softmax_path
+from tests._paths import CSR_CASES, csr_path, hub_mode, route_parts, softmax_path
 from tests.test_matmul_routes_gpu import ROUTES as MATMUL_ROUTES
 from tests.test_scatter_routes_gpu import ROUTES as SCATTER_ROUTES
 from tests.test_special_values_gpu import SOFTMAX_CASES, SPECIAL_CSR_CASES
@@ -504,7 +504,9 @@ def csr_variants(op, dtype, K, R, E, seed, names=PTR_VARIANTS):
     return out
 
 
-def csr_call(op):
+def csr_call(op, routes):
+    """`routes` collects what ops.csr_last_route() says after every forward: at capture and in the eager calls (the backward
+    runs on autograd's thread, which has a last route of its own)."""
     def call(inp, outs):
         out = plain(outs[0]) if outs else None
         if op == 'gather':
@@ -516,6 +518,7 @@ def csr_call(op):
             res = ops.segment_mean_csr(inp['x'], inp['ptr'], out=out)
         else:
             res = (ops.segment_min_csr if op == 'min' else ops.segment_max_csr)(inp['x'], inp['ptr'])
+        routes.append(ops.csr_last_route())
         val = res[0] if isinstance(res, tuple) else res
         gx, = torch.autograd.grad(val, inp['x'], inp['g'])
         return (res[0], res[1], gx) if isinstance(res, tuple) else (val, gx)
@@ -530,7 +533,11 @@ def csr_case(path, op, names=PTR_VARIANTS, seed=0):
     variants = csr_variants(op, dtype, K, R, E, seed=seed + K + R, names=names)
     inp = static_inputs(variants[0][1], grad=('x',))
     out_specs = {'gather': [((E, K), dtype, None)], 'sum': [((R, K), dtype, None)], 'mean': [((R, K), dtype, None)]}.get(op, [])
-    check_replays(csr_call(op), inp, variants, csr_reference(op, R), out_specs)
+    routes = []
+    check_replays(csr_call(op, routes), inp, variants, csr_reference(op, R), out_specs)
+    # at capture and in every eager call: the kernel of the case, and the chunk kernels on the scratch the operators bring
+    want = ('gather' if op == 'gather' else 'segment', got_path, hub_mode(E, cut, R, True))
+    assert routes and {route_parts(r) for r in routes} == {want}, (path, op, routes)
 
 
 @pytest.mark.parametrize('op', CSR_OPS)
@@ -570,8 +577,9 @@ SOFTMAX_TOL = {torch.float32: [(2e-4, 1e-9), (2e-3, 2e-6)], torch.float64: [(1e-
 def test_softmax_csr_forward_and_backward(name, dtype):
     _, outer, inner, (groups, lo, hi, hub), path, bpath = _SOFTMAX_TABLE[name]
     D = groups * ((lo + hi) // 2)
-    assert (softmax_path(dtype, outer, D, inner, groups)[0], softmax_path(dtype, outer, D, inner, groups, backward=True)[0]) == \
-        (path, bpath)
+    got_path, cut = softmax_path(dtype, outer, D, inner, groups)
+    assert (got_path, softmax_path(dtype, outer, D, inner, groups, backward=True)[0]) == (path, bpath)
+    routes = []
     gen = torch.Generator().manual_seed(groups + inner)
     variants = [(v, {'x': ints(gen, (outer, D, inner), -5, 5).to(dtype), 'g': ints(gen, (outer, D, inner), -2, 2).to(dtype),
                      'ptr': to_ptr(ptr_lengths(v, groups, D))}) for v in PTR_VARIANTS]
@@ -579,10 +587,13 @@ def test_softmax_csr_forward_and_backward(name, dtype):
 
     def call(i, _outs):
         y = ops.softmax_csr(i['x'], i['ptr'], 1)
+        routes.append(ops.csr_last_route())       # (the forward's: the backward runs on autograd's thread)
         gx, = torch.autograd.grad(y, i['x'], i['g'])
         return y, gx
 
     check_replays(call, inp, variants, softmax_reference, tols=SOFTMAX_TOL[dtype])
+    want = ('softmax', path, hub_mode(D, cut, groups, False))
+    assert routes and {route_parts(r) for r in routes} == {want}, (name, routes)
 
 
 # ======================================================================================================================

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from tests._guard import assert_no_poison, big_value, guarded, guarded_copy, poisoned
-from tests._paths import CSR_CASES, _csr_shape, _lens, csr_path
+from tests._paths import CSR_CASES, _csr_shape, _lens, csr_path, hub_mode, route_parts
 
 pytestmark = pytest.mark.gpu
 ROOT = osp.dirname(osp.dirname(osp.abspath(__file__)))
@@ -54,6 +54,7 @@ def lib():
     L = c.CDLL(osp.join(ROOT, 'pyg_lib_amd', 'libpyg_hip.so'))
     L.pyg_hip_last_error.restype = c.c_char_p
     L.pyg_hip_matmul_last_variant.restype = c.c_char_p
+    L.pyg_hip_csr_last_route.restype = c.c_char_p
     _sig(L, 'pyg_hip_matmul_workspace_size', SZ, [I64])
     _sig(L, 'pyg_hip_segment_matmul', I32, [I32, P, P, I32, P, P, P, I64, I64, I64, I64, P, SZ, I32, P])
     _sig(L, 'pyg_hip_grouped_matmul', I32, [I32, P, I64, P, SZ, I32, P])
@@ -516,6 +517,8 @@ def test_segment_csr(lib, name, dtype, K, leading, spec, path, with_ws):
         ok(lib, lib.pyg_hip_segment_csr_ws(op, code, src.data_ptr(), ip.data_ptr(), 0 if shared else rows + 1, out.data_ptr(),
                                            ptr(arg), 1, leading, rows, E, K, ptr(ws), ws_bytes, stream()))
         torch.cuda.synchronize()
+        route = lib.pyg_hip_csr_last_route().decode()       # the library ran the kernels the case was built for
+        assert route_parts(route) == ('segment', path, hub_mode(E, cut, leading * rows, with_ws)), (name, op, route)
         g.check()
         if op != 0:
             assert_no_poison(out, f'segment_csr op {op} out')
@@ -566,6 +569,8 @@ def test_gather_csr(lib, name, dtype, K, leading, spec, with_ws):
     ok(lib, lib.pyg_hip_gather_csr_ws(CODE[dtype], src.data_ptr(), ip.data_ptr(), 0, out.data_ptr(), leading, rows, E, K,
                                       ptr(ws), ws_bytes, stream()))
     torch.cuda.synchronize()
+    route = lib.pyg_hip_csr_last_route().decode()
+    assert route_parts(route) == ('gather', path, hub_mode(E, cut, leading * rows, with_ws)), (name, route)
     g.check()
     assert_no_poison(out, 'gather_csr out')
     want = torch.repeat_interleave(data, torch.from_numpy(np.diff(ips[0])), dim=1)

@@ -29,8 +29,8 @@ import torch
 
 import oracle
 from pyg_lib_amd import diagnostics, ops
-from tests._paths import (CAS, CSR_CASES, DET, FRESH, MAX, MIN, MUL, SORTED, SUM, _csr_shape, csr_path, scatter_path,
-                          softmax_path)
+from tests._paths import (CAS, CSR_CASES, DET, FRESH, MAX, MIN, MUL, SORTED, SUM, _csr_shape, csr_path, hub_mode, route_parts,
+                          scatter_path, softmax_path)
 from tests.golden import special_cases as SC
 
 pytestmark = pytest.mark.gpu
@@ -49,6 +49,7 @@ def lib():
     L = c.CDLL(osp.join(ROOT, 'pyg_lib_amd', 'libpyg_hip.so'))
     L.pyg_hip_last_error.restype = c.c_char_p
     L.pyg_hip_scatter_last_route.restype = c.c_char_p
+    L.pyg_hip_csr_last_route.restype = c.c_char_p
     for name, res, args in (
             ('pyg_hip_scatter_workspace_size', SZ, [I64, I64, I64]),
             ('pyg_hip_scatter', I32, [I32, I32, P, P, I64, I64, I64, P, P, P, I64, I64, I64, I64, I32, P, SZ, P]),
@@ -310,6 +311,7 @@ def test_gathers_copy_every_bit_on_every_kernel(name, dtype, K, spec, kernel):
     want = torch.repeat_interleave(table, torch.from_numpy(np.diff(ips[0])), dim=0)
     assert {'nan', '+inf', '-inf', '-0'} <= classes_in(to_np(want), dtype == torch.bfloat16)
     got = ops.gather_csr(table.to(DEV), torch.from_numpy(ips[0]).to(DEV))
+    assert route_parts(ops.csr_last_route()) == ('gather', kernel, hub_mode(E, cut, rows, True)), (name, ops.csr_last_route())
     SC.same_bits(to_np(got), to_np(want), dtype == torch.bfloat16, nan_bits=True, what=f'gather_csr {name}')
     # gather_coo of the same rows: 16-byte slices where the row is whole slices, elements otherwise
     index = torch.repeat_interleave(torch.arange(rows), torch.from_numpy(np.diff(ips[0])))
@@ -412,6 +414,8 @@ def test_segment_csr_paths(lib, name, dtype, K, leading, spec, path, with_ws, fr
                                            arg.data_ptr() if arg is not None else None, fresh, leading, rows,
                                            E, K, ws.data_ptr() if ws is not None else None, ws_bytes, stream()))
         torch.cuda.synchronize()
+        route = lib.pyg_hip_csr_last_route().decode()      # ... and the library ran that kernel, and the hub kernels of the case
+        assert route_parts(route) == ('segment', path, hub_mode(E, cut, leading * rows, with_ws)), (name, opn, route)
         # (the oracle's mean ignores `out`; its sum of a fresh output starts from +0)
         seed = None if fresh else to_np(out0)
         want, warg = oracle.segment_csr(op, to_np(data), ips[:1] if shared else ips, seed, odt(dtype))
@@ -628,6 +632,9 @@ def test_scatter_paths(lib, name, dtype, op, flags, with_ws, B, E, K, N, path):
             diagnostics.set_float_atomic_mode(before)
         what = f'{name} [{mode}{"+CAS flag" if mode_flags else ""}{" fresh" if fresh_minmax else ""}]'
         assert lib.pyg_hip_scatter_last_route().decode() == path, what       # ... and the library ran the path of the label
+        if hub_cut is not None:       # ... on the row kernel of the label; the hub rows' scratch is the workspace's dead part
+            route = lib.pyg_hip_csr_last_route().decode()
+            assert route_parts(route) == ('segment', ROW_KERNEL[name], hub_mode(E, hub_cut, B * N, True)), (what, route)
         fresh = bool(flags & FRESH) or fresh_minmax
         if op != MUL:
             assert want_classes(opn, fresh) <= classes_in(want, bf16), (what, classes_in(want, bf16))
@@ -749,7 +756,7 @@ def test_softmax_paths(name, outer, inner, spec, path, bpath, dtype):
     f64 = int(dtype == torch.float64)
     path, bpath = (path if isinstance(path, str) else path[f64]), (bpath if isinstance(bpath, str) else bpath[f64])
     got_path, cut = softmax_path(dtype, outer, D, inner, groups)
-    got_bpath = softmax_path(dtype, outer, D, inner, groups, backward=True)[0]
+    got_bpath, bcut = softmax_path(dtype, outer, D, inner, groups, backward=True)
     assert (got_path, got_bpath) == (path, bpath), (name, got_path, got_bpath)
     assert (lens.max() > cut) == (hub > 0), (name, int(lens.max()), cut)
     if path == 'lanes1' and not hub and lo <= 1:
@@ -765,6 +772,7 @@ def test_softmax_paths(name, outer, inner, spec, path, bpath, dtype):
     rtol = 1e-11 if dtype == torch.float64 else 2e-4 if loose else 2e-6
     pd = torch.from_numpy(ptr).to(DEV)
     got = ops.softmax_csr(x.to(DEV), pd, 1)
+    assert route_parts(ops.csr_last_route()) == ('softmax', path, hub_mode(D, cut, groups, False)), (name, ops.csr_last_route())
     check_forward(to_np(got), want, xn, rtol, f'{name} forward')
     # backward: `out` = the expected forward (exact zeros and NaN groups included); out_grad: small integers, and an Inf / a
     # NaN in head 0 of two clean groups
@@ -776,6 +784,7 @@ def test_softmax_paths(name, outer, inner, spec, path, bpath, dtype):
         dy[0, ptr[groups // 3] + min(2047, hub - 1), inner - 1] = float('-inf')
     gwant = oracle.softmax_csr_backward(want, to_np(dy), ptr, 1)
     gin = torch.ops.pyg.softmax_csr_backward(torch.from_numpy(want).to(DEV), dy.to(DEV), pd, 1)
+    assert route_parts(ops.csr_last_route()) == ('softmax_bwd', bpath, hub_mode(D, bcut, groups, False)), (name, ops.csr_last_route())
     assert np.isnan(gwant).any() and (gwant == 0).any()
     brtol, batol = (1e-9, 1e-14) if dtype == torch.float64 else (2e-3 if loose else 1e-5, 2e-6)
     check_backward(to_np(gin), gwant, want, brtol, batol, f'{name} backward')
