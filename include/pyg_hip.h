@@ -57,6 +57,7 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  19: pyg_hip_node2vec_walk (second-order (p, q) random walks, keyed and deterministic).
  *  18: pyg_hip_csr_route, pyg_hip_csr_last_route (which kernels serve a CSR reduction, gather or softmax: asked without
  *      running, told after).
  *  17: pyg_hip_graclus / _graclus_route / _graclus_last_route / _graclus_tile / _graclus_workspace_size / _graclus_pending_error
@@ -83,7 +84,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 18
+#define PYG_HIP_ABI_VERSION 19
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -634,6 +635,39 @@ PYG_HIP_API int pyg_hip_segment_concat(const int64_t* const* bases, const int64_
 PYG_HIP_API int pyg_hip_random_walk(int index_dtype, const void* rowptr, int64_t num_nodes, const void* col,
                                     int64_t num_edges, const void* seed, int64_t num_seeds, const float* rand,
                                     int64_t walk_length, void* out, void* stream);
+
+/*
+ * node2vec walks: second-order random walks with return parameter p and in-out parameter q (this build only; the
+ * reference's pyg::random_walk stops at p = q = 1).  Buffers and the treatment of nodes outside the graph are those of
+ * pyg_hip_random_walk.  The result is a pure function of the arguments: the same on the device, on the binding's CPU key
+ * and in tests/_node2vec_ref.py, bit for bit.  One lane per walk; no atomics, no allocation, no synchronisation.
+ *
+ * Word stream.  Walk i is the i-th seed.  Its stream of 32-bit words is the successive results of
+ * at::Philox4_32(key, subsequence = i, offset = 0)::operator() (ATen/core/PhiloxRNGEngine.h): Philox4x32-10 with key = the
+ * two halves of `key`, counter = (n_lo, n_hi, i_lo, i_hi) for the n-th block of four words, outputs consumed in index
+ * order 0..3.
+ * Uniform.  A word becomes u = float(word >> 8) * 2^-24, in [0, 1).
+ * Thresholds.  The caller computes them once in double and rounds to float32: M = max(1/p, 1, 1/q), a_ret = (1/p)/M,
+ * a_near = 1/M, a_far = (1/q)/M.  Each must lie in (0, 1] (else PYG_HIP_ERR_INVALID).
+ * Stays.  A current node v outside [0, num_nodes), or whose rowptr pair is empty or leaves [0, num_edges], makes the walk
+ * stay and consumes no words.
+ * Step 1 (no predecessor).  One word: v1 = col[rs + min(trunc(u * float(deg)), deg - 1)].
+ * Step j >= 2.  Predecessor t = out[j-2], current v = out[j-1].  Up to max_attempts attempts of two words each: the first
+ * word gives the candidate x = col[rs_v + o] as in step 1, the second gives r; accept if r < a, where a = a_ret if x == t,
+ * else a_near if the value x occurs in row t of col (binary search over col[rs_t, re_t): the edge t -> x exists), else
+ * a_far.  Row t is the rowptr pair validated when t was current; if t stayed (no valid row) the row is empty.  With
+ * a_near == a_far the search is skipped.
+ * Precondition.  col ascending within each row (duplicates and self loops allowed).  On unsorted rows the walk is still a
+ * walk over edges and every read stays in bounds; only the bias is unspecified.
+ * Fallback.  If all max_attempts attempts are rejected, one more word u draws exactly: position k of row v has the weight
+ * a_ret / a_near / a_far of col[rs_v + k]; total = the sum of the weights in position order, in double;
+ * target = double(u) * total; the first k whose double prefix sum exceeds target is taken, else deg - 1.  The running time
+ * is therefore bounded for any p and q.  0 <= max_attempts <= 1024; 0 sends every biased step through the fallback.
+ */
+PYG_HIP_API int pyg_hip_node2vec_walk(int index_dtype, const void* rowptr, int64_t num_nodes, const void* col,
+                                      int64_t num_edges, const void* seed, int64_t num_seeds, int64_t walk_length,
+                                      float a_ret, float a_near, float a_far, uint64_t key, int max_attempts, void* out,
+                                      void* stream);
 
 /*
  * Induced subgraph of a node list.  Replaces pyg::subgraph (schema pyg_lib/csrc/sampler/subgraph.cpp:30-32; CPU kernel

@@ -12,7 +12,7 @@ _HERE = osp.dirname(osp.abspath(__file__))
 _LIB = None
 
 OK = 0
-ABI_VERSION = 18  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
+ABI_VERSION = 19  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
 DTYPES = {
     torch.float32: 0,
     torch.float64: 1,
@@ -201,6 +201,11 @@ def lib() -> ctypes.CDLL:
         L.pyg_hip_graclus.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p, c.c_int64, c.c_int64, c.c_int,
                                       c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p]
         L.pyg_hip_graclus_pending_error.restype = c.c_int
+        # node2vec_walk (include/pyg_hip.h, "node2vec walks")
+        # (index_dtype, rowptr, N, col, E, seed, S, L, a_ret, a_near, a_far, key, max_attempts, out, stream)
+        L.pyg_hip_node2vec_walk.restype = c.c_int
+        L.pyg_hip_node2vec_walk.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64,
+                                            c.c_float, c.c_float, c.c_float, c.c_uint64, c.c_int, c.c_void_p, c.c_void_p]
         _LIB = L
     return _LIB
 

@@ -241,6 +241,61 @@ def random_walk(
     return torch.ops.pyg.random_walk(rowptr, col, seed, walk_length, p, q)
 
 
+def node2vec_walk(
+    rowptr: Tensor,
+    col: Tensor,
+    seed: Tensor,
+    walk_length: int,
+    p: float = 1.0,
+    q: float = 1.0,
+) -> Tensor:
+    r"""Second-order random walks of the `"node2vec: Scalable Feature Learning for Networks"
+    <https://arxiv.org/abs/1607.00653>`_ paper, for any return parameter :obj:`p` and in-out parameter :obj:`q` (this
+    build only; :func:`random_walk` keeps the reference's limit ``p = q = 1``).
+
+    From the second step on, a neighbour :obj:`x` of the current node is taken with a weight that depends on the previous
+    node :obj:`t`: :obj:`1 / p` if ``x == t``, :obj:`1` if the edge ``t -> x`` exists, :obj:`1 / q` otherwise.  The law is
+    exact for every :obj:`p`, :obj:`q` (rejection sampling with an exact fallback after 32 rejected attempts).
+
+    :obj:`col` must be ascending within each row (``torch_geometric.utils.sort_edge_index`` order); on unsorted rows the
+    result is still a walk over edges but its bias is unspecified.  One 64-bit key is drawn from the torch generator of
+    the tensors' device, so ``torch.manual_seed`` reproduces a call; the walks themselves are :func:`node2vec_walk_keyed`
+    with that key.  Cannot be captured into a graph (the key is drawn on the host): capture the keyed form.
+
+    Args:
+        rowptr: Compressed source node indices.
+        col: Target node indices, ascending within each row.
+        seed: Seed node indices from where random walks start.
+        walk_length: The walk length of a random walk.
+        p: Likelihood of immediately revisiting a node in the walk (finite, > 0).
+        q: Control parameter to interpolate between breadth-first strategy and depth-first strategy (finite, > 0).
+
+    Returns:
+        A tensor of shape :obj:`[seed.size(0), walk_length + 1]` of the seeds' dtype.
+    """
+    return torch.ops.pyg.node2vec_walk(rowptr, col, seed, walk_length, p, q)
+
+
+def node2vec_walk_keyed(
+    rowptr: Tensor,
+    col: Tensor,
+    seed: Tensor,
+    walk_length: int,
+    p: float,
+    q: float,
+    key: int,
+    max_attempts: int = 32,
+) -> Tensor:
+    r"""The deterministic core of :func:`node2vec_walk`: a pure function of its arguments, the same bit for bit on a HIP
+    device and on the CPU (DESIGN.md 2.16 is the specification).  Walk ``i`` consumes the words of
+    ``at::Philox4_32(key, subsequence=i)``; :obj:`key` is a signed 64-bit integer read as its 64 bits.  A biased step
+    makes up to :obj:`max_attempts` rejection attempts (``0 <= max_attempts <= 1024``) and then draws exactly from the
+    row's weights, so its running time is bounded for any :obj:`p`, :obj:`q`; ``max_attempts = 0`` takes the exact draw
+    at every biased step.  Makes no host read and allocates only its output: capturable with ``torch.cuda.graph``.
+    """
+    return torch.ops.pyg.node2vec_walk_keyed(rowptr, col, seed, walk_length, p, q, key, max_attempts)
+
+
 def release_table_cache() -> int:
     """Hands the node tables the sampler keeps between calls (up to 8 x 128 MiB per device) back to the caching allocator;
     returns how many are still in use by running calls.  ``torch.cuda.empty_cache()`` afterwards returns the memory to
@@ -270,4 +325,5 @@ def last_mode() -> str:
 
 
 __all__ = ['neighbor_sample', 'hetero_neighbor_sample', 'subgraph', 'random_walk', 'neighbor_sample_batched',
-           'hetero_neighbor_sample_batched', 'release_table_cache', 'last_mode', 'rng_carry_stats']
+           'hetero_neighbor_sample_batched', 'release_table_cache', 'last_mode', 'rng_carry_stats', 'node2vec_walk',
+           'node2vec_walk_keyed']
