@@ -9,6 +9,7 @@
 #include <ATen/record_function.h>
 #include <dlfcn.h>
 
+#include <optional>
 #include <string>
 #include <tuple>
 
@@ -73,6 +74,14 @@ struct RoctxRange {
 
 inline void check_status(int rc) {
   TORCH_CHECK(rc == PYG_HIP_OK, pyg_hip_last_error());
+}
+
+// The autograd functions of the ops that take `out` return no gradient for it: a given `out` that requires grad would lose
+// it without a word.  Called by the Autograd-key fronts before apply() (inside forward() grad mode is off).
+inline void check_out_needs_no_grad(const char* name, const std::optional<Tensor>& out) {
+  TORCH_CHECK(!(out.has_value() && out->defined() && out->requires_grad() && at::GradMode::is_enabled()), name,
+              ": the gradient with respect to a given 'out' is not implemented ('out' requires grad); pass out.detach() "
+              "or call under torch.no_grad()");
 }
 
 // PyTorch-ROCm types HIP devices/streams as "cuda" (masquerading), hence these spellings.

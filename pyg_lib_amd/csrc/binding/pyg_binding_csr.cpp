@@ -318,12 +318,16 @@ class SegmentMeanCSR : public torch::autograd::Function<SegmentMeanCSR> {
       grad_in = call_gather_csr(grad_out, indptr, grad_in);
       auto indptr1 = indptr.narrow(-1, 0, indptr.size(-1) - 1);
       auto indptr2 = indptr.narrow(-1, 1, indptr.size(-1) - 1);
-      auto count = (indptr2 - indptr1).to(grad_in.options());
+      // (16-bit gradients: the row lengths stay in float32 -- bf16 holds no integer above 256 exactly, and a rounded length
+      // plus the rounding of the division is more than one ulp; the division below then runs in float32 and rounds once)
+      const bool half = grad_in.scalar_type() == at::kBFloat16 || grad_in.scalar_type() == at::kHalf;
+      const auto count_options = half ? grad_in.options().dtype(at::kFloat) : grad_in.options();
+      auto count = (indptr2 - indptr1).to(count_options);
       // broadcast counts back to the source positions; uncovered positions divide by 1
       auto count_shape = std::vector<int64_t>(src_shape.begin(), src_shape.begin() + indptr.dim());
       auto rows_shape = count_shape;
       rows_shape.back() = count.size(-1);
-      auto count_e = at::ones(count_shape, grad_in.options());
+      auto count_e = at::ones(count_shape, count_options);
       count_e = call_gather_csr(count.expand(rows_shape), indptr, count_e);
       for (int64_t i = 0; i < grad_out.dim() - indptr.dim(); ++i) count_e = count_e.unsqueeze(-1);
       grad_in.true_divide_(count_e);
@@ -407,22 +411,27 @@ class SoftmaxCSR : public torch::autograd::Function<SoftmaxCSR> {
 };
 
 Tensor segment_sum_csr_autograd(const Tensor& src, const Tensor& indptr, const std::optional<Tensor>& out) {
+  check_out_needs_no_grad("segment_sum_csr", out);
   return SegmentSumCSR::apply(src, indptr, out)[0];
 }
 Tensor segment_mean_csr_autograd(const Tensor& src, const Tensor& indptr, const std::optional<Tensor>& out) {
+  check_out_needs_no_grad("segment_mean_csr", out);
   return SegmentMeanCSR::apply(src, indptr, out)[0];
 }
 std::tuple<Tensor, Tensor> segment_min_csr_autograd(const Tensor& src, const Tensor& indptr,
                                                     const std::optional<Tensor>& out) {
+  check_out_needs_no_grad("segment_min_csr", out);
   auto r = SegmentMinMaxCSR<true>::apply(src, indptr, out);
   return std::make_tuple(r[0], r[1]);
 }
 std::tuple<Tensor, Tensor> segment_max_csr_autograd(const Tensor& src, const Tensor& indptr,
                                                     const std::optional<Tensor>& out) {
+  check_out_needs_no_grad("segment_max_csr", out);
   auto r = SegmentMinMaxCSR<false>::apply(src, indptr, out);
   return std::make_tuple(r[0], r[1]);
 }
 Tensor gather_csr_autograd(const Tensor& src, const Tensor& indptr, const std::optional<Tensor>& out) {
+  check_out_needs_no_grad("gather_csr", out);
   return GatherCSR::apply(src, indptr, out)[0];
 }
 Tensor softmax_csr_autograd(const Tensor& src, const Tensor& ptr, int64_t dim) {

@@ -454,19 +454,23 @@ class ScatterFwdBwd : public torch::autograd::Function<ScatterFwdBwd<OP>> {
 
 Tensor scatter_sum_autograd(const Tensor& src, const Tensor& index, int64_t dim, const std::optional<Tensor>& out,
                             std::optional<int64_t> dim_size) {
+  check_out_needs_no_grad("scatter_sum", out);
   return ScatterFwdBwd<OP_SUM>::apply(src, index, dim, out, dim_size)[0];
 }
 Tensor scatter_mul_autograd(const Tensor& src, const Tensor& index, int64_t dim, const std::optional<Tensor>& out,
                             std::optional<int64_t> dim_size) {
+  check_out_needs_no_grad("scatter_mul", out);
   return ScatterFwdBwd<OP_MUL>::apply(src, index, dim, out, dim_size)[0];
 }
 std::tuple<Tensor, Tensor> scatter_min_autograd(const Tensor& src, const Tensor& index, int64_t dim,
                                                 const std::optional<Tensor>& out, std::optional<int64_t> dim_size) {
+  check_out_needs_no_grad("scatter_min", out);
   auto r = ScatterFwdBwd<OP_MIN>::apply(src, index, dim, out, dim_size);
   return std::make_tuple(r[0], r[1]);
 }
 std::tuple<Tensor, Tensor> scatter_max_autograd(const Tensor& src, const Tensor& index, int64_t dim,
                                                 const std::optional<Tensor>& out, std::optional<int64_t> dim_size) {
+  check_out_needs_no_grad("scatter_max", out);
   auto r = ScatterFwdBwd<OP_MAX>::apply(src, index, dim, out, dim_size);
   return std::make_tuple(r[0], r[1]);
 }
@@ -519,6 +523,7 @@ class ScatterMean : public torch::autograd::Function<ScatterMean> {
 
 Tensor scatter_mean_autograd(const Tensor& src, const Tensor& index, int64_t dim, const std::optional<Tensor>& out,
                              std::optional<int64_t> dim_size) {
+  check_out_needs_no_grad("scatter_mean", out);
   return ScatterMean::apply(src, index, dim, out, dim_size)[0];
 }
 
@@ -536,7 +541,8 @@ class SegmentSumCOO : public torch::autograd::Function<SegmentSumCOO> {
     at::AutoDispatchBelowADInplaceOrView g;
     static auto op = find_op<CooFn>("pyg::segment_sum_coo");
     auto out = op.call(src, index, optional_out, dim_size);
-    ctx->save_for_backward({index});
+    // the forward broadcasts index up to src.shape[:index.dim()]; gather_coo does not: the backward gets the expanded one
+    ctx->save_for_backward({expand_coo_index(src, index)});
     if (optional_out.has_value()) ctx->mark_dirty({optional_out.value()});
     return {out};
   }
@@ -558,7 +564,10 @@ class SegmentMeanCOO : public torch::autograd::Function<SegmentMeanCOO> {
     TORCH_CHECK(dim >= 0, "segment_mean_coo: index must have at least 1 dimension");
     auto index_b = expand_coo_index(src, index);
     auto out = mean.call(src, index, optional_out, dim_size);
-    auto ones = at::ones(index_b.sizes(), out.options());
+    // (16-bit sources: the bucket sizes are counted and kept in float32 -- bf16 holds no integer above 256 exactly, and a
+    // rounded size plus the rounding of the backward's division is more than one ulp)
+    const bool half = out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kHalf;
+    auto ones = at::ones(index_b.sizes(), half ? out.options().dtype(at::kFloat) : out.options());
     auto count = sum.call(ones, index_b, std::nullopt, out.size(dim));
     ctx->save_for_backward({index_b, count});
     ctx->saved_data["src_shape"] = src.sizes();
@@ -639,25 +648,30 @@ class GatherCOO : public torch::autograd::Function<GatherCOO> {
 
 Tensor segment_sum_coo_autograd(const Tensor& src, const Tensor& index, const std::optional<Tensor>& out,
                                 std::optional<int64_t> dim_size) {
+  check_out_needs_no_grad("segment_sum_coo", out);
   return SegmentSumCOO::apply(src, index, out, dim_size)[0];
 }
 Tensor segment_mean_coo_autograd(const Tensor& src, const Tensor& index, const std::optional<Tensor>& out,
                                  std::optional<int64_t> dim_size) {
+  check_out_needs_no_grad("segment_mean_coo", out);
   return SegmentMeanCOO::apply(src, index, out, dim_size)[0];
 }
 std::tuple<Tensor, Tensor> segment_min_coo_autograd(const Tensor& src, const Tensor& index,
                                                     const std::optional<Tensor>& out,
                                                     std::optional<int64_t> dim_size) {
+  check_out_needs_no_grad("segment_min_coo", out);
   auto r = SegmentMinMaxCOO<true>::apply(src, index, out, dim_size);
   return std::make_tuple(r[0], r[1]);
 }
 std::tuple<Tensor, Tensor> segment_max_coo_autograd(const Tensor& src, const Tensor& index,
                                                     const std::optional<Tensor>& out,
                                                     std::optional<int64_t> dim_size) {
+  check_out_needs_no_grad("segment_max_coo", out);
   auto r = SegmentMinMaxCOO<false>::apply(src, index, out, dim_size);
   return std::make_tuple(r[0], r[1]);
 }
 Tensor gather_coo_autograd(const Tensor& src, const Tensor& index, const std::optional<Tensor>& out) {
+  check_out_needs_no_grad("gather_coo", out);
   return GatherCOO::apply(src, index, out)[0];
 }
 

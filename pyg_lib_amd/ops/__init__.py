@@ -323,6 +323,13 @@ def _require_float(name: str, src: Tensor) -> None:
         raise ValueError(f'{name} requires a floating-point src tensor (got {src.dtype})')
 
 
+def _require_no_grad_out(name: str, out: Optional[Tensor]) -> None:
+    # as the typed ops: no gradient is computed for a given `out`
+    if out is not None and out.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(f"{name}: the gradient with respect to a given 'out' is not implemented ('out' requires grad); "
+                           f"pass out.detach() or call under torch.no_grad()")
+
+
 def scatter_softmax(src: Tensor, index: Tensor, dim: int = -1, dim_size: Optional[int] = None) -> Tensor:
     r"""Softmax over the groups given by :obj:`index` (pyg_lib/ops/__init__.py:838-862): recentre by
     the per-group max, exponentiate, divide by the per-group sum."""
@@ -348,8 +355,11 @@ def scatter_log_softmax(src: Tensor, index: Tensor, dim: int = -1, dim_size: Opt
 def scatter_std(src: Tensor, index: Tensor, dim: int = -1, out: Optional[Tensor] = None,
                 dim_size: Optional[int] = None, unbiased: bool = True) -> Tensor:
     r"""Standard deviation per group (pyg_lib/ops/__init__.py:892-931): two :func:`scatter_sum`
-    passes, Bessel's correction ``N / (N - 1)`` when :obj:`unbiased`."""
+    passes, Bessel's correction ``N / (N - 1)`` when :obj:`unbiased`.  A group of one element has the value 0, where the
+    square root has no finite derivative: the gradient is NaN for that one element and right for every other, as in the
+    reference."""
     _require_float('scatter_std', src)
+    _require_no_grad_out('scatter_std', out)
     if out is not None:
         dim_size = out.size(dim)
     idx = _broadcast(index, src, dim)
@@ -367,6 +377,7 @@ def scatter_logsumexp(src: Tensor, index: Tensor, dim: int = -1, out: Optional[T
     r"""Numerically stable log-sum-exp per group (pyg_lib/ops/__init__.py:934-984).  Empty buckets
     give ``0`` for a fresh output and keep the caller's value when :obj:`out` is supplied."""
     _require_float('scatter_logsumexp', src)
+    _require_no_grad_out('scatter_logsumexp', out)
     if out is not None:
         dim_size = out.size(dim)
     size = list(src.size())
