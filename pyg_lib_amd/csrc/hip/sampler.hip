@@ -1816,7 +1816,12 @@ int run_sampler(int num_node_types, int num_relations, const pyg_hip_relation* r
       cleanup();
       return PYG_HIP_OK;
     }
-    PYG_HIP_REQUIRE(r.num_cols < (1ll << 31) || W == 0, "sampler: biased sampling supports rows below 2^31 neighbours");
+    // the limit is on the relation's edge count, whatever the length of its rows; a hop that draws nothing (W == 0) passes
+    if (r.num_cols >= (1ll << 31) && W != 0) {
+      cleanup();
+      return fail(PYG_HIP_ERR_INVALID, "sampler: biased sampling needs a relation of fewer than 2^31 edges (this one has %lld)",
+                  (long long)r.num_cols);
+    }
     if (W > 0) {
       rc = rng_wait32(c, rng, out_base + W, nullptr);
       if (rc != PYG_HIP_OK) return rc;
