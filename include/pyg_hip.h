@@ -1366,9 +1366,19 @@ PYG_HIP_API const char* pyg_hip_csr_last_route(void);
  * Device hash map key -> first position: the kernels behind torch.classes.pyg.CUDAHashMap
  * (pyg_lib/csrc/classes/cuda/hash_map.cu:36-100, a cuco::static_map wrapper in the reference).
  * The table is caller-owned: `slots` = pyg_hip_hash_map_slots(n, load_factor) entries (a power of two)
- * of table_keys (uint64) and table_vals (int64).  Keys are int16 / int32 / int64; INT64_MIN is the empty
- * sentinel, as in the reference.  `build` leaves the number of distinct keys in *distinct_dev (device
- * memory); duplicate keys map to their first position.  `get` writes the position or -1 per query.
+ * of table_keys (uint64) and table_vals (int64).  Keys are int16 / int32 / int64 (widened with sign extension).
+ * `build` leaves the number of distinct keys in *distinct_dev (device memory); duplicate keys map to their first
+ * position.  `get` writes the position or -1 per query.
+ *
+ * INT64_MIN is reserved: it marks an empty slot, as cuco's empty-key sentinel does in the reference.  `build` skips a
+ * key equal to it -- the key touches neither table array and is not counted in *distinct_dev, the positions of the
+ * other keys are unchanged -- and `get` answers -1 for it on every table.  (The minima of int16 and int32 widen to other
+ * values and are ordinary keys.)
+ *
+ * pyg_hip_hash_map_slots: the smallest power of two >= 16 that is >= max(n, 1) / load_factor + 1, so at least one slot
+ * stays empty; a load factor outside (0, 1] counts as 0.5.  -1 if n < 0 or if no power of two below 2^62 is large enough
+ * (a denormal load factor).  build / get return PYG_HIP_ERR_INVALID, before anything is launched, for a dtype other than
+ * the three above, `slots` that is no power of two or (build) not greater than n, and NULL arrays.
  */
 PYG_HIP_API int64_t pyg_hip_hash_map_slots(int64_t n, double load_factor);
 PYG_HIP_API int pyg_hip_hash_map_build(int key_dtype, const void* keys, int64_t n, uint64_t* table_keys,

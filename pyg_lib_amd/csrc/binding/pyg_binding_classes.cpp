@@ -1,6 +1,8 @@
 // torch.classes.pyg.CUDAHashMap on the HIP device (pyg_lib/csrc/classes/cuda/hash_map.cu:103-203: same
 // class name, constructor, methods and pickle contract; kernels csrc/hip/hash_map.hip through the
 // C-ABI).  "CUDA" is how PyTorch-ROCm names the HIP device.
+#include <limits>
+
 #include <torch/custom_class.h>
 #include <torch/library.h>
 
@@ -21,15 +23,24 @@ struct CUDAHashMap : torch::CustomClassHolder {
     DeviceGuard guard(key.device());
     key_ = key.clone();
     slots_ = pyg_hip_hash_map_slots(key.numel(), load_factor);
+    TORCH_CHECK(slots_ > 0, "CUDAHashMap: no table of fewer than 2^62 slots holds ", key.numel(), " keys at load factor ",
+                load_factor);
     const auto opts = key.options().dtype(at::kLong);
     table_keys_ = at::empty({slots_}, opts);
     table_vals_ = at::empty({slots_}, opts);
-    auto distinct = at::empty({1}, opts);
+    auto info = at::zeros({2}, opts);  // [0] number of distinct keys, [1] whether the reserved key occurs
     check_status(pyg_hip_hash_map_build(dtype_code(key.scalar_type()), key_.data_ptr(), key_.numel(),
                                         reinterpret_cast<uint64_t*>(table_keys_.data_ptr<int64_t>()),
-                                        table_vals_.data_ptr<int64_t>(), slots_, distinct.data_ptr<int64_t>(),
+                                        table_vals_.data_ptr<int64_t>(), slots_, info.data_ptr<int64_t>(),
                                         current_stream(key_)));
-    size_ = distinct.item<int64_t>();
+    // INT64_MIN marks an empty slot (cuco's empty-key sentinel in the reference): the kernel skips it, the class refuses
+    // it.  int16 / int32 keys widen to other values.  The flag rides on the copy that fetches the size.
+    if (key_.scalar_type() == at::kLong && key_.numel() > 0)
+      info.select(0, 1).copy_(key_.eq(std::numeric_limits<int64_t>::min()).any());
+    const auto host = info.cpu();
+    TORCH_CHECK(host.data_ptr<int64_t>()[1] == 0, "CUDAHashMap: key ", std::numeric_limits<int64_t>::min(),
+                " (INT64_MIN) is reserved as the empty-slot marker and cannot be stored");
+    size_ = host.data_ptr<int64_t>()[0];
   }
 
   Tensor get(const Tensor& query) {

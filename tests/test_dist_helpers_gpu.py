@@ -9,6 +9,7 @@ import torch
 import oracle
 import pyg_lib_amd  # noqa: F401
 from pyg_lib_amd import sampler
+from tests import _hash_ref as R
 from tests.golden import sampler_reference_vectors as G
 
 pytestmark = pytest.mark.gpu
@@ -176,3 +177,120 @@ def test_hetero_relabel_reproduces_hetero_sample(csc, disjoint):
         # ... and both equal the sampler's own relabelling
         assert ref_row[e].tolist() == out[0][e].tolist() and ref_col[e].tolist() == out[1][e].tolist()
     assert sum(len(v) for v in out[0].values()) > 500
+
+
+# ---- relabel_neighborhood at its own edges: the table's floor and first doubling, the scan tile, the find-or-claim loop ------
+def _cap(S, E):
+    """Slots of relabel's table: the smallest power of two >= 1024 that is >= 2 (S + E)."""
+    cap = 1024
+    while cap < 2 * (S + E):
+        cap *= 2
+    return cap
+
+
+def _relabel_ref(seed, sampled, counts, batch, disjoint):
+    """The dictionary of oracle.relabel_neighborhood without its Python loop (for E in the millions; compared with the oracle
+    itself below): ids in order of first occurrence over the seeds, then the sampled sequence; disjoint keys are (batch, node)."""
+    S = len(seed)
+    key = np.concatenate([seed, sampled]).astype(np.int64)
+    if disjoint:
+        big = int(key.max()) + 1
+        key = np.concatenate([np.arange(S), batch]).astype(np.int64) * big + key
+    _, first, inverse = np.unique(key, return_index=True, return_inverse=True)
+    rank = np.empty(first.size, dtype=np.int64)
+    rank[np.argsort(first)] = np.arange(first.size)
+    return np.repeat(np.arange(len(counts)), counts), rank[inverse.reshape(-1)][S:]
+
+
+def _counts(rng, E, nsrc):
+    counts = rng.multinomial(E, np.ones(nsrc) / nsrc) if nsrc > 1 else np.array([E])
+    assert counts.sum() == E
+    return counts.tolist()
+
+
+def _relabel_patterns(rng, S, E):
+    """(name, seed, sampled, batch or None) for every pattern that S allows."""
+    ids = rng.permutation(1_000_000)[:S + E]
+    seed = ids[:S]
+    yield 'all distinct', seed, ids[S:], None
+    yield 'all equal', seed, np.full(E, 1_000_001), None
+    yield 'few values', seed, rng.integers(0, 40, E), None
+    if S:
+        yield 'every sampled node a seed', seed, seed[rng.integers(0, S, E)], None
+        yield 'all equal to the last seed', seed, np.full(E, seed[-1]), None
+        dup = np.arange(7)[rng.integers(0, 7, S)] if S > 1 else seed
+        yield 'duplicated seeds', dup, rng.integers(0, 14, E), None
+        batch = rng.integers(0, S, E)
+        nodes = rng.integers(0, 12, E)                    # the same nodes again and again, under different batch ids
+        yield 'disjoint', rng.integers(0, 12, S), nodes, batch
+        yield 'disjoint, every key a seed key', seed, seed[batch], batch
+        yield 'disjoint, duplicated seeds', np.full(S, 5), np.full(E, 5), batch
+
+
+def _relabel_case(S, E, seed, sampled, counts, batch, tag):
+    disjoint = batch is not None
+    want = oracle.relabel_neighborhood(seed, sampled, counts, None, batch, False, disjoint)
+    fast = _relabel_ref(seed, sampled, counts, batch, disjoint)
+    assert np.array_equal(want[0], fast[0]) and np.array_equal(want[1], fast[1]), tag   # the restatement, on every small case
+    got = torch.ops.pyg.relabel_neighborhood(dev(seed), dev(sampled), counts, 1_000_002, dev(batch) if disjoint else None, False,
+                                             disjoint)
+    assert np.array_equal(got[0].cpu().numpy(), want[0]), tag
+    bad = np.flatnonzero(got[1].cpu().numpy() != want[1])
+    assert bad.size == 0, (tag, bad.size, bad[:5], got[1].cpu().numpy()[bad[:5]], want[1][bad[:5]])
+
+
+RELABEL_SIZES = [(S, half - S) for half in (511, 512, 513) for S in (0, 1, 300)] + \
+                [(1, 1023), (300, 1024), (0, 1025), (300, 2047), (1, 2049), (0, 2047), (300, 1023)]
+
+
+def test_relabel_at_table_and_scan_tile_edges():
+    """2 (S + E) = 1022 | 1024 | 1026: the 1024-slot floor of the table, filled to exactly one half, and its first doubling;
+    E = 1023 .. 1025, 2047, 2049: one scan tile, one element more, two tiles, one element more.  Every pattern at every size,
+    in one test item: each assertion names its (pattern, S, E).  Then 1000 node ids that share one home slot."""
+    for S, E in RELABEL_SIZES:
+        _relabel_sizes(S, E)
+    _relabel_of_1000_nodes_with_one_home_slot()
+
+
+def _relabel_sizes(S, E):
+    rng = np.random.default_rng(1000 * S + E)
+    assert _cap(S, E) == (1024 if S + E <= 512 else 2048 if S + E <= 1024 else 4096 if S + E <= 2048 else 8192), (S, E)
+    seen = 0
+    for name, seed, sampled, batch in _relabel_patterns(rng, S, E):
+        assert len(seed) == S and len(sampled) == E and (batch is None or (len(batch) == E and 0 <= batch.min() and batch.max() < S))
+        _relabel_case(S, E, seed, sampled, _counts(rng, E, max(S, 3)), batch, (name, S, E))
+        seen += 1
+    assert seen == (9 if S else 3), (S, E)
+
+
+def _relabel_of_1000_nodes_with_one_home_slot():
+    """Node ids that all hash to the last slot of the 2048-slot table (the key of a non-disjoint call is the node id, the
+    mixer is hash_map.hip's): one chain of up to 1000 slots across the wrap, claimed by 1000 racing threads."""
+    rng = np.random.default_rng(2047)
+    S, E = 300, 700
+    assert _cap(S, E) == 2048
+    ids = rng.permutation(R.keys_homed_at(2047, 2048, 1000, np.int64))[:1000]
+    assert np.unique(ids).size == 1000 and (R.home(ids, 2048) == 2047).all()
+    for with_duplicates in (False, True):
+        sampled = ids[rng.integers(0, 1000, E)] if with_duplicates else ids[S:]
+        distinct = np.unique(np.concatenate([ids[:S], sampled])).size
+        assert 600 < distinct < 1000 if with_duplicates else distinct == 1000
+        _relabel_case(S, E, ids[:S], sampled, _counts(rng, E, S), None, ('one home slot', with_duplicates))
+
+
+def test_relabel_through_the_three_launch_scan():
+    """E = 2048 * 1024 + 1 is 2049 scan tiles, one more than the apply kernel sums up by itself: the first-occurrence flags are
+    scanned in three launches (tile sums, their scan, apply)."""
+    rng = np.random.default_rng(2049)
+    S, E = 300, 2048 * 1024 + 1
+    seed = rng.integers(0, 3_000_000, S)
+    counts = _counts(rng, E, 1000)
+    for name, sampled, batch in (('random', rng.integers(0, 3_000_000, E), None),
+                                 ('all equal', np.full(E, 17), None),
+                                 ('disjoint', rng.integers(0, 5000, E), rng.integers(0, S, E))):
+        want = _relabel_ref(seed, sampled, counts, batch, batch is not None)
+        assert want[1].max() + 1 >= (500_000 if name != 'all equal' else S)   # the case has the distinct keys it is meant to have
+        got = torch.ops.pyg.relabel_neighborhood(dev(seed), dev(sampled), counts, 3_000_000, dev(batch) if batch is not None else None,
+                                                 False, batch is not None)
+        assert np.array_equal(got[0].cpu().numpy(), want[0]), name
+        assert np.array_equal(got[1].cpu().numpy(), want[1]), name
