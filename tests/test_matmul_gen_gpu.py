@@ -3,8 +3,10 @@
 The reference's grouped GEMM carries one problem size per group (pyg_lib/csrc/ops/cuda/matmul_kernel.cu:33-67) and
 its own tests use K = 16 / 9 / 32 with M = 48 / 42 / 64, plain and transposed (test/ops/test_matmul.py:56-72).
 Everything here must run an `mfma_*_gen` kernel, never the one-thread-per-output fallback.
-Tolerances as in test_matmul_gpu.py: fp32 <= 1e-5 norm-wise, 16-bit within one rounding of the correctly rounded
-result; integer-valued inputs bit-exact.
+Tolerances as in test_matmul_gpu.py: fp32 <= 1e-5 norm-wise; 16-bit rtol = 2^-7 (bf16) / 2^-9 (fp16) plus an absolute term
+against the correctly rounded result -- a whole ulp, which bounds the error but cannot tell round-to-nearest-even from
+truncation or a partial sum kept in 16 bits; integer-valued inputs bit-exact, on sums that (almost) never need rounding.
+That the kernel's one rounding IS to nearest even is pinned bit for bit by test_matmul_exact_gpu.py.
 """
 import numpy as np
 import pytest

@@ -4,8 +4,10 @@ ROUTES below is a literal table (call description) -> name reported by ``ops.mat
 not derived: every call was issued on commit 342fbda -- the last one whose forward dispatch was a chain of ``if``s inside
 matmul.hip -- and the name it reported was written down.  The table pins the route choice across refactors of the
 dispatcher: it holds at least one call for every name the library can report and crosses every rule of the choice
-(include/pyg_hip.h, ``PYG_HIP_MM_SCHED_*``) on both sides.  Values are not checked here (test_matmul_gpu.py,
-test_matmul_gen_gpu.py and test_stress_gpu.py do that).
+(include/pyg_hip.h, ``PYG_HIP_MM_SCHED_*``) on both sides.  The operands here are zeros and only the name is asserted;
+test_matmul_exact_gpu.py issues the same calls (through `run_call(desc, fill)`) on integer data whose sums need rounding and
+compares the output bits, so every row of the table with a 16-bit or fp32 product is checked for its name AND its values.
+test_matmul_gpu.py, test_matmul_gen_gpu.py and test_stress_gpu.py compare random data within a tolerance.
 
 A call description is ``(op, dtype, K, M, B, rows, schedule, extra)``:
   op        'seg' = segment_matmul, 'grp' = grouped_matmul with B groups
@@ -453,28 +455,45 @@ class _ByteShifted:
                                          'data': (self.base.data_ptr() + 1, False), 'version': 2}
 
 
-def _matrix(rows, cols, dtype, extra, keep):
+def _matrix(rows, cols, dtype, extra, keep, data=None):
+    """A zero [rows, cols] operand with the alignment `extra` asks for; `data` (a CPU tensor of that shape and dtype) fills it."""
     if 'byte1' in extra:
         keep.append(_ByteShifted(rows, cols, dtype))
+        if data is not None:   # byte for byte into the allocation: no kernel has to write through the odd address
+            keep[-1].base[1:1 + data.numel() * data.element_size()] = data.contiguous().view(-1).view(torch.uint8).to(DEV)
         t = torch.as_tensor(keep[-1], device=DEV)
         assert t.data_ptr() % t.element_size() == 1
         return t
     if 'off1' in extra:
         t = torch.zeros(1 + rows * cols, dtype=DTYPES[dtype], device=DEV)[1:].view(rows, cols)
         assert t.data_ptr() % 16 == t.element_size()
-        return t
-    return torch.zeros(rows, cols, dtype=DTYPES[dtype], device=DEV)
+    else:
+        t = torch.zeros(rows, cols, dtype=DTYPES[dtype], device=DEV)
+    if data is not None:
+        assert data.shape == t.shape and data.dtype == t.dtype
+        t.copy_(data)
+    return t
 
 
-def run_call(desc):
-    """Issue the call `desc` describes and return the variant name it reports."""
-    op, dtype, K, M, B, rows, sched, extra = desc
-    extra = set(extra.split('+')) - {''}
+def call_sizes(desc):
+    """(total rows, rows per relation) of a call description (needs the device for a (c, d) row count)."""
+    rows, B = desc[5], desc[4]
     if isinstance(rows, tuple):
         rows = rows[0] * torch.cuda.get_device_properties(0).multi_processor_count + rows[1]
     sizes = [rows // B] * B if B else []
     if B:
         sizes[-1] += rows - sum(sizes)
+    return rows, sizes
+
+
+def run_call(desc, fill=None):
+    """Issue the call `desc` describes and return the variant name it reports.  With `fill` -- a function
+    (relation b, its rows, K, M, torch dtype) -> CPU tensors (X_b [rows, K], W_b [K, M]) -- the operands hold that data
+    instead of zeros (same sizes, views, schedule and precision), and the result is (name, outputs per relation)."""
+    op, dtype, K, M, B, rows, sched, extra = desc
+    extra = set(extra.split('+')) - {''}
+    rows, sizes = call_sizes(desc)
+    data = [fill(b, r, K, M, DTYPES[dtype]) for b, r in enumerate(sizes)] if fill else None
     keep = []
     prev = torch.get_float32_matmul_precision()
     try:
@@ -482,21 +501,29 @@ def run_call(desc):
         ops.set_matmul_schedule(sched)
         if op == 'seg':
             ptr = torch.tensor([0] + torch.tensor(sizes, dtype=torch.long).cumsum(0).tolist())
-            x = _matrix(rows, K, dtype, extra, keep)
+            x = _matrix(rows, K, dtype, extra, keep, torch.cat([d[0] for d in data]) if data else None)
             w = torch.zeros(B, K, M, dtype=DTYPES[dtype], device=DEV)
+            if data:
+                w.copy_(torch.stack([d[1] for d in data]))
             out = ops.segment_matmul(x, ptr, w)
             assert out.shape == (rows, M)
+            outs = [out[ptr[b]:ptr[b + 1]] for b in range(B)]
         else:
-            xs = [_matrix(r, K, dtype, extra, keep) for r in sizes]
+            xs = [_matrix(r, K, dtype, extra, keep, data[b][0] if data else None) for b, r in enumerate(sizes)]
             if 'trans' in extra:
-                ws = [torch.zeros(M, K, dtype=DTYPES[dtype], device=DEV).t() for _ in sizes]
+                ws = [torch.zeros(M, K, dtype=DTYPES[dtype], device=DEV) for _ in sizes]
             else:
                 ws = [torch.zeros(K, M, dtype=DTYPES[dtype], device=DEV) for _ in sizes]
+            if data:
+                for b, wb in enumerate(ws):
+                    wb.copy_(data[b][1].t() if 'trans' in extra else data[b][1])
+            if 'trans' in extra:
+                ws = [wb.t() for wb in ws]
             outs = ops.grouped_matmul(xs, ws)
             assert [tuple(o.shape) for o in outs] == [(r, M) for r in sizes]
         name = ops.matmul_last_variant()
         torch.cuda.synchronize()
-        return name
+        return (name, outs) if fill else name
     finally:
         ops.set_matmul_schedule('auto')
         torch.set_float32_matmul_precision(prev)
