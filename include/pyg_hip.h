@@ -57,6 +57,8 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  20: pyg_hip_rgcn_route, pyg_hip_rgcn_last_route (which kernel family serves a fused R-GCN call: asked without running,
+ *      told after).
  *  19: pyg_hip_node2vec_walk (second-order (p, q) random walks, keyed and deterministic).
  *  18: pyg_hip_csr_route, pyg_hip_csr_last_route (which kernels serve a CSR reduction, gather or softmax: asked without
  *      running, told after).
@@ -84,7 +86,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 19
+#define PYG_HIP_ABI_VERSION 20
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -316,8 +318,8 @@ PYG_HIP_API size_t pyg_hip_rgcn_fused_workspace_size(int64_t num_relations, int6
  * (pyg_lib/csrc/ops/cuda/segment_coo_kernel.cu:1316-1360, ops/cuda/matmul_kernel.cu:304-319,
  * ops/cuda/scatter_kernel.cu:56-71): the gathered rows and the messages never exist in HBM.
  *   x [num_x_rows, K], out [num_out_rows, M] (ACCUMULATED into: zero it for a plain aggregation), both `dtype`
- *   (PYG_BF16 / PYG_F16) row-major; K = M = 128 (other shapes: PYG_HIP_ERR_UNSUPPORTED, the caller keeps the
- *   three-op chain).  Messages are rounded to `dtype` once (as the chain does), runs of equal destination are
+ *   row-major; which types and shapes are served: the table of pyg_hip_rgcn_route below (others:
+ *   PYG_HIP_ERR_UNSUPPORTED, the caller keeps the three-op chain).  Messages are rounded to `dtype` once (as the chain does), runs of equal destination are
  *   summed in fp32 and added with packed 16-bit atomics.  `relations` is a host array.  `checked` is a bit field
  *   (PYG_HIP_RGCN_*): PYG_HIP_RGCN_CAS makes the packed adds compare-and-swap loops (see pyg_hip_set_float_atomic_mode).
  *   Never synchronises -- unless PYG_HIP_RGCN_CHECKED is set: then every gather / scatter index is validated against num_x_rows (x_rows, gather_map_len)
@@ -340,10 +342,8 @@ PYG_HIP_API int pyg_hip_rgcn_pending_error(void);
  * sums every row's source features in fp32 in edge order, multiplies the 32 sums of a relation with its weight in one
  * MFMA tile, accumulates the relations of a row in fp32 and WRITES every row of `out` once (rows without edges: zeros).
  *   - `out` is OVERWRITTEN, not accumulated into (do not zero it); it must be 16-byte aligned;
- *   - K and M may be any multiples of 8 up to 256 (the feature rows are walked per 128-feature slice, W travels through
- *     LDS in 128 x 128 chunks; K, M in {128, 256} have pipelined instances, the others one instance with run-time row sizes
- *     and masked lanes); dtype may also be PYG_F32 with K, M multiples of 4 up to 128 (fp32 sums; 128 x 128: fp32
- *     MFMAs, otherwise FMAs);
+ *   - more types and shapes than the atomic kernel's (the table of pyg_hip_rgcn_route below): the feature rows are walked
+ *     per 128-feature slice, W travels through LDS in 128 x 128 chunks;
  *   - the same bits on every run; rounding: the per-relation feature sum and the result are each rounded once;
  *   - the workspace is pyg_hip_rgcn_grouped_workspace_size() bytes (4 bytes per row of every relation's destination
  *     segment -- scatter_rows, or the rows of `out` at and behind its scatter_offset if that is 0: row starts, touched
@@ -358,6 +358,41 @@ PYG_HIP_API size_t pyg_hip_rgcn_grouped_workspace_size(const pyg_hip_rgcn_relati
 PYG_HIP_API int pyg_hip_rgcn_fused(int dtype, const void* x, int64_t num_x_rows, const pyg_hip_rgcn_relation* relations,
                                    int64_t num_relations, void* out, int64_t num_out_rows, int64_t K, int64_t M,
                                    int checked, void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * Which kernel family serves a call.  pyg_hip_rgcn_route(dtype, K, M, num_relations, flags) answers without touching a device
+ * (`flags`: the `checked` bit field; only PYG_HIP_RGCN_GROUPED matters).  The first row that applies:
+ *
+ *   flags      dtype        K, M                                          route
+ *   any        any          num_relations < 0 or >= 2^30                  unsupported
+ *   GROUPED    any          num_relations > 512                           unsupported
+ *   -          bf16, f16    128 x 128                                     atomic             packed 16-bit atomic adds
+ *   -          anything else                                              unsupported
+ *   GROUPED    bf16, f16    128 x 128                                     grouped_128        the four-deep item pipeline
+ *   GROUPED    bf16, f16    128 x 256, 256 x 128, 256 x 256               grouped_shape      the pipeline over 128-feature sub-items
+ *   GROUPED    bf16, f16    other multiples of 8 in [8, 256]              grouped_small      run-time row sizes, item at a time
+ *   GROUPED    f32          128 x 128                                     grouped_f32        fp32 sums, fp32 MFMAs
+ *   GROUPED    f32          other multiples of 4 in [4, 128]              grouped_f32_small  run-time row sizes, FMAs
+ *   GROUPED    anything else                                              unsupported
+ *
+ * pyg_hip_rgcn_fused refuses an unsupported call (PYG_HIP_ERR_UNSUPPORTED; a dtype no row names: PYG_HIP_ERR_INVALID).  What a
+ * route does not decide follows from the call: with up to 24 relations their records travel in the kernel argument (`inline`),
+ * longer lists are staged through the workspace (`staged`); a feature table of 4 GB or more takes the instances with 64-bit row
+ * offsets (`big`); PYG_HIP_RGCN_CHECKED / _DEFERRED select the validating instances of atomic and grouped_128 (`check`; the
+ * other families always validate and report only with one of the two flags).
+ * pyg_hip_rgcn_last_route() names the last launch of the calling thread:
+ *   "<route> kc<KC> mc<MC> <bf16|f16|f32> <check|nocheck> <big|nobig> <inline|staged>"
+ * (KC, MC: the 128-feature slices of a feature row / a row of `out` the kernel is instantiated for), "none" before the first
+ * one; a call that launches nothing (no relations, no edges) leaves it as it is.
+ */
+#define PYG_HIP_RGCN_ROUTE_UNSUPPORTED 0
+#define PYG_HIP_RGCN_ROUTE_ATOMIC 1
+#define PYG_HIP_RGCN_ROUTE_GROUPED_128 2
+#define PYG_HIP_RGCN_ROUTE_GROUPED_SHAPE 3
+#define PYG_HIP_RGCN_ROUTE_GROUPED_SMALL 4
+#define PYG_HIP_RGCN_ROUTE_GROUPED_F32 5
+#define PYG_HIP_RGCN_ROUTE_GROUPED_F32_SMALL 6
+PYG_HIP_API int pyg_hip_rgcn_route(int dtype, int64_t K, int64_t M, int64_t num_relations, int flags);
+PYG_HIP_API const char* pyg_hip_rgcn_last_route(void);
 
 /* ---- neighbor_sample / hetero_neighbor_sample ---------------------------------------------- */
 

@@ -12,7 +12,7 @@ _HERE = osp.dirname(osp.abspath(__file__))
 _LIB = None
 
 OK = 0
-ABI_VERSION = 19  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
+ABI_VERSION = 20  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
 DTYPES = {
     torch.float32: 0,
     torch.float64: 1,
@@ -73,6 +73,10 @@ def lib() -> ctypes.CDLL:
         L.pyg_hip_set_float_atomic_mode.argtypes = [c.c_int]
         L.pyg_hip_last_accumulate_info.restype = c.c_char_p
         L.pyg_hip_rgcn_pending_error.restype = c.c_int
+        # (dtype, K, M, num_relations, flags) -> PYG_HIP_RGCN_ROUTE_*
+        L.pyg_hip_rgcn_route.restype = c.c_int
+        L.pyg_hip_rgcn_route.argtypes = [c.c_int, c.c_int64, c.c_int64, c.c_int64, c.c_int]
+        L.pyg_hip_rgcn_last_route.restype = c.c_char_p
         L.pyg_hip_atomic_selftest.restype = c.c_int
         L.pyg_hip_atomic_selftest.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_char_p, c.c_size_t, c.c_void_p]
         # (fn, dtype, left, left_rows, right, right_rows, index_dtype, left_index, right_index, out, E, F, stream)

@@ -300,13 +300,58 @@ static void rgcn_index_checks(const at::TensorList gather_index, const at::Tenso
               scatter_index[r].device(), " vs ", like.device(), ")");
 }
 
+// The feature tables of rgcn_fused_tables: relation r gathers row node_id[gather_type[r]][gather_index[r][e]] of
+// feat[gather_type[r]] (contiguous copies of both).  rgcn_fused has none: every relation reads the call's x at its gather_offset.
+struct RgcnTables {
+  const std::vector<Tensor>& feat;
+  const std::vector<Tensor>& node_id;
+  at::IntArrayRef gather_type;
+};
+
+// The relation array, the workspace and the call of both operators.  `like`: a feature tensor (device, stream); x / x_rows: the
+// call's own feature matrix (rgcn_fused) or nullptr / 0 with `tables`.
 // `grouped`: every scatter_index is nondecreasing (the samplers' `row`): the atomic-free owner-computes kernel
 // (PYG_HIP_RGCN_GROUPED) WRITES `out` -- deterministic, no zero fill needed; verified on the device (rgcn_check_flags)
-static at::Tensor rgcn_workspace(const std::vector<pyg_hip_rgcn_relation>& rels, int64_t E, int64_t out_rows, bool grouped,
-                                 const at::TensorOptions& like) {
-  const size_t bytes = grouped ? pyg_hip_rgcn_grouped_workspace_size(rels.data(), (int64_t)rels.size(), out_rows)
-                               : pyg_hip_rgcn_fused_workspace_size((int64_t)rels.size(), E);
-  return at::empty({(int64_t)bytes}, like.dtype(at::kByte));
+static Tensor rgcn_call(const Tensor& like, const void* x, int64_t x_rows, const at::TensorList gather_index,
+                        const at::TensorList scatter_index, const int64_t* gather_offset, at::IntArrayRef scatter_offset,
+                        const Tensor& wc, Tensor out, bool grouped, at::OptionalIntArrayRef scatter_rows, const RgcnTables* tables) {
+  const size_t R = gather_index.size();
+  std::vector<pyg_hip_rgcn_relation> rels(R);
+  std::vector<Tensor> keep;
+  int64_t E = 0;
+  for (size_t r = 0; r < R; ++r) {
+    rgcn_index_checks(gather_index, scatter_index, like, r);
+    auto g = gather_index[r].contiguous();
+    auto s = scatter_index[r].contiguous();
+    rels[r] = pyg_hip_rgcn_relation{};
+    rels[r].gather_index = g.data_ptr<int64_t>();
+    rels[r].scatter_index = s.data_ptr<int64_t>();
+    rels[r].num_edges = g.numel();
+    rels[r].gather_offset = gather_offset ? gather_offset[r] : 0;
+    rels[r].scatter_offset = scatter_offset[r];
+    rels[r].scatter_rows = scatter_rows.has_value() ? (*scatter_rows)[r] : 0;
+    rels[r].weight = static_cast<const char*>(wc.data_ptr()) + (int64_t)r * wc.size(1) * wc.size(2) * wc.element_size();
+    if (tables) {
+      TORCH_CHECK(tables->gather_type[r] >= 0 && (size_t)tables->gather_type[r] < tables->feat.size(),
+                  "rgcn_fused_tables: gather_type out of range");
+      const Tensor& f = tables->feat[(size_t)tables->gather_type[r]];
+      const Tensor& n = tables->node_id[(size_t)tables->gather_type[r]];
+      rels[r].x = f.data_ptr();
+      rels[r].gather_map = n.data_ptr<int64_t>();
+      rels[r].x_rows = f.size(0);
+      rels[r].gather_map_len = n.numel();
+    }
+    E += g.numel();
+    keep.push_back(g);
+    keep.push_back(s);
+  }
+  const size_t bytes = grouped ? pyg_hip_rgcn_grouped_workspace_size(rels.data(), (int64_t)R, out.size(0))
+                               : pyg_hip_rgcn_fused_workspace_size((int64_t)R, E);
+  auto ws = at::empty({(int64_t)bytes}, like.options().dtype(at::kByte));
+  check_status(pyg_hip_rgcn_fused(dtype_code(wc.scalar_type()), x, x_rows, rels.data(), (int64_t)R, out.data_ptr(), out.size(0),
+                                  wc.size(1), out.size(1), rgcn_check_flags() | (grouped ? PYG_HIP_RGCN_GROUPED : 0),
+                                  ws.data_ptr(), (size_t)ws.numel(), current_stream(like)));
+  return out;
 }
 
 Tensor rgcn_fused_kernel(const Tensor& x, const at::TensorList gather_index, const at::TensorList scatter_index,
@@ -329,32 +374,8 @@ Tensor rgcn_fused_kernel(const Tensor& x, const at::TensorList gather_index, con
   TORCH_CHECK(out.is_contiguous(), "rgcn_fused: 'out' must be contiguous");
   DeviceGuard guard(x.device());
   const auto xc = x.contiguous();
-  const auto wc = weight.contiguous();
-  std::vector<pyg_hip_rgcn_relation> rels(R);
-  std::vector<Tensor> keep;
-  int64_t E = 0;
-  for (size_t r = 0; r < R; ++r) {
-    rgcn_index_checks(gather_index, scatter_index, x, r);
-    auto g = gather_index[r].contiguous();
-    auto s = scatter_index[r].contiguous();
-    rels[r] = pyg_hip_rgcn_relation{};
-    rels[r].gather_index = g.data_ptr<int64_t>();
-    rels[r].scatter_index = s.data_ptr<int64_t>();
-    rels[r].num_edges = g.numel();
-    rels[r].gather_offset = gather_offset[r];
-    rels[r].scatter_offset = scatter_offset[r];
-    rels[r].scatter_rows = scatter_rows.has_value() ? (*scatter_rows)[r] : 0;
-    rels[r].weight = static_cast<const char*>(wc.data_ptr()) + (int64_t)r * wc.size(1) * wc.size(2) * wc.element_size();
-    E += g.numel();
-    keep.push_back(g);
-    keep.push_back(s);
-  }
-  auto ws = rgcn_workspace(rels, E, out.size(0), grouped, x.options());
-  check_status(pyg_hip_rgcn_fused(dtype_code(x.scalar_type()), xc.data_ptr(), xc.size(0), rels.data(), (int64_t)R,
-                                  out.data_ptr(), out.size(0), xc.size(1), out.size(1),
-                                  rgcn_check_flags() | (grouped ? PYG_HIP_RGCN_GROUPED : 0), ws.data_ptr(), (size_t)ws.numel(),
-                                  current_stream(x)));
-  return out;
+  return rgcn_call(x, xc.data_ptr(), xc.size(0), gather_index, scatter_index, gather_offset.data(), scatter_offset,
+                   weight.contiguous(), out, grouped, scatter_rows, nullptr);
 }
 
 // The same without the per-batch feature matrix: relation r gathers row node_id[gather_type[r]][gather_index[r][e]] of
@@ -378,7 +399,6 @@ Tensor rgcn_fused_tables_kernel(const at::TensorList feat, const at::TensorList 
               "rgcn_fused_tables: expected weight [R, K, M], out [N_out, M]");
   TORCH_CHECK(out.is_contiguous() && out.scalar_type() == weight.scalar_type(), "rgcn_fused_tables: 'out' must be contiguous and typed like 'weight'");
   DeviceGuard guard(f0.device());
-  std::vector<Tensor> keep;
   std::vector<Tensor> fc(T), nc(T);
   for (size_t t = 0; t < T; ++t) {
     TORCH_CHECK(feat[t].dim() == 2 && feat[t].size(1) == weight.size(1) && feat[t].scalar_type() == weight.scalar_type() &&
@@ -389,36 +409,9 @@ Tensor rgcn_fused_tables_kernel(const at::TensorList feat, const at::TensorList 
     fc[t] = feat[t].contiguous();
     nc[t] = node_id[t].contiguous();
   }
-  const auto wc = weight.contiguous();
-  std::vector<pyg_hip_rgcn_relation> rels(R);
-  int64_t E = 0;
-  for (size_t r = 0; r < R; ++r) {
-    rgcn_index_checks(gather_index, scatter_index, f0, r);
-    TORCH_CHECK(gather_type[r] >= 0 && (size_t)gather_type[r] < T, "rgcn_fused_tables: gather_type out of range");
-    auto g = gather_index[r].contiguous();
-    auto s = scatter_index[r].contiguous();
-    const size_t t = (size_t)gather_type[r];
-    rels[r] = pyg_hip_rgcn_relation{};
-    rels[r].gather_index = g.data_ptr<int64_t>();
-    rels[r].scatter_index = s.data_ptr<int64_t>();
-    rels[r].num_edges = g.numel();
-    rels[r].gather_offset = 0;
-    rels[r].scatter_offset = scatter_offset[r];
-    rels[r].scatter_rows = scatter_rows.has_value() ? (*scatter_rows)[r] : 0;
-    rels[r].weight = static_cast<const char*>(wc.data_ptr()) + (int64_t)r * wc.size(1) * wc.size(2) * wc.element_size();
-    rels[r].x = fc[t].data_ptr();
-    rels[r].gather_map = nc[t].data_ptr<int64_t>();
-    rels[r].x_rows = fc[t].size(0);
-    rels[r].gather_map_len = nc[t].numel();
-    E += g.numel();
-    keep.push_back(g);
-    keep.push_back(s);
-  }
-  auto ws = rgcn_workspace(rels, E, out.size(0), grouped, f0.options());
-  check_status(pyg_hip_rgcn_fused(dtype_code(weight.scalar_type()), nullptr, 0, rels.data(), (int64_t)R, out.data_ptr(),
-                                  out.size(0), wc.size(1), out.size(1), rgcn_check_flags() | (grouped ? PYG_HIP_RGCN_GROUPED : 0),
-                                  ws.data_ptr(), (size_t)ws.numel(), current_stream(f0)));
-  return out;
+  const RgcnTables tables{fc, nc, gather_type};
+  return rgcn_call(f0, nullptr, 0, gather_index, scatter_index, nullptr, scatter_offset, weight.contiguous(), out, grouped,
+                   scatter_rows, &tables);
 }
 
 // Autograd, mirroring SegmentMatmul (pyg_lib/csrc/ops/autograd/matmul_kernel.cpp:68-111).

@@ -461,26 +461,299 @@ int deferred_error_slot(int** out) {
 
 #include "rgcn_grouped.h"
 
+// ---- the route: the table of pyg_hip_rgcn_route in pyg_hip.h, the one place that decides which kernel family a call runs ------
+enum class Route {
+  kUnsupported = PYG_HIP_RGCN_ROUTE_UNSUPPORTED,
+  kAtomic = PYG_HIP_RGCN_ROUTE_ATOMIC,                         // rgcn_fused_kernel
+  kGrouped128 = PYG_HIP_RGCN_ROUTE_GROUPED_128,                // rgcn_grouped_kernel
+  kGroupedShape = PYG_HIP_RGCN_ROUTE_GROUPED_SHAPE,            // rgcn_grouped_shape_kernel<KC, MC>
+  kGroupedSmall = PYG_HIP_RGCN_ROUTE_GROUPED_SMALL,            // rgcn_grouped_small_kernel
+  kGroupedF32 = PYG_HIP_RGCN_ROUTE_GROUPED_F32,                // rgcn_grouped_f32_kernel
+  kGroupedF32Small = PYG_HIP_RGCN_ROUTE_GROUPED_F32_SMALL,     // rgcn_grouped_f32_small_kernel
+};
+
+// what the type and the shape say, whatever the relation count
+Route shape_route(int dtype, int64_t K, int64_t M, bool grouped) {
+  const bool half = dtype == PYG_BF16 || dtype == PYG_F16;
+  if (!grouped) return half && K == 128 && M == 128 ? Route::kAtomic : Route::kUnsupported;
+  if (dtype == PYG_F32) {   // rows of multiples of 16 bytes up to 512
+    if (K < 4 || K > 128 || M < 4 || M > 128 || K % 4 != 0 || M % 4 != 0) return Route::kUnsupported;
+    return K == 128 && M == 128 ? Route::kGroupedF32 : Route::kGroupedF32Small;
+  }
+  if (!half || K < 8 || K > 256 || M < 8 || M > 256 || K % 8 != 0 || M % 8 != 0) return Route::kUnsupported;
+  if (K == 128 && M == 128) return Route::kGrouped128;
+  return (K == 128 || K == 256) && (M == 128 || M == 256) ? Route::kGroupedShape : Route::kGroupedSmall;
+}
+
+// THE choice.  Pure: no HIP call, no global.
+Route choose_rgcn_route(int dtype, int64_t K, int64_t M, int64_t R, int flags) {
+  const bool grouped = (flags & PYG_HIP_RGCN_GROUPED) != 0;
+  if (R < 0 || R >= (1 << 30) || (grouped && R > kGroupedMaxRel)) return Route::kUnsupported;
+  return shape_route(dtype, K, M, grouped);
+}
+
+// What follows from a route and the call's numbers; the launch code follows it, pyg_hip_rgcn_last_route reports it.
+struct RgcnPlan {
+  Route route = Route::kUnsupported;
+  int dtype = 0;
+  int KC = 1, MC = 1;           // 128-feature slices of a feature row / of a row of `out` the kernel is instantiated for
+  int lds = 0;                  // dynamic LDS of the main kernel
+  int per_cu = 0;               // persistent grid: workgroups per CU
+  bool inl = false;             // the records travel in the kernel argument (R <= kRgcnInline), else through the workspace
+  bool ck = false;              // index errors are reported (PYG_HIP_RGCN_CHECKED or _DEFERRED)
+  bool big = false;             // some feature table is 4 GB or more: 64-bit row offsets (fill_relations)
+  const void* kern = nullptr;   // rgcn_kernel(plan)
+};
+
+RgcnPlan rgcn_plan(Route route, int dtype, int64_t K, int64_t M, int64_t R) {
+  RgcnPlan p;
+  p.route = route;
+  p.dtype = dtype;
+  p.inl = R <= kRgcnInline;
+  if (route == Route::kAtomic) {   // 32 KB of W + an 8 KB stage per wave: two workgroups per CU
+    p.lds = 32768 + 4 * 8192;
+    p.per_cu = 2;
+    return p;
+  }
+  if (route == Route::kGroupedShape) p.KC = (int)(K / 128), p.MC = (int)(M / 128);
+  else if (route != Route::kGrouped128) p.KC = p.MC = 2;   // (run-time row sizes, fp32: the instance with two 256-byte slices)
+  // 16-bit: 32 KB of W, 32-row A tiles, three workgroups per CU (<= 168 VGPRs, 44 KB of LDS); fp32: all 64 KB of W, an A tile of
+  // 16 rows of 528 bytes, two workgroups per CU (rgcn_grouped.h)
+  const bool wide = dtype == PYG_F32;
+  p.lds = (wide ? 65536 + 8704 : 32768 + 8192 * p.KC) + 2 * 4 * kGroupedMaxRel;
+  p.per_cu = wide ? 2 : 3;
+  return p;
+}
+
+// a run-time bool as a type: f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+const void* with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// The instance of the plan's family.  grouped_128 and atomic exist with and without CHECK; the other families always validate.
+const void* rgcn_kernel(const RgcnPlan& p) {
+  return with_bool(p.dtype == PYG_BF16, [&](auto bf) {
+    return with_bool(p.big, [&](auto bg) {
+      return with_bool(p.inl, [&](auto in) -> const void* {
+        constexpr bool BF = decltype(bf)::value, BIG = decltype(bg)::value, INL = decltype(in)::value;
+        switch (p.route) {
+          case Route::kAtomic:
+            return with_bool(p.ck, [](auto ck) { return (const void*)&rgcn_fused_kernel<BF, decltype(ck)::value, BIG, INL>; });
+          case Route::kGrouped128:
+            return with_bool(p.ck, [](auto ck) { return (const void*)&rgcn_grouped_kernel<BF, decltype(ck)::value, BIG, INL>; });
+          case Route::kGroupedShape:
+            if (p.KC == 2 && p.MC == 2) return (const void*)&rgcn_grouped_shape_kernel<BF, BIG, INL, 2, 2>;
+            if (p.KC == 1) return (const void*)&rgcn_grouped_shape_kernel<BF, BIG, INL, 1, 2>;
+            return (const void*)&rgcn_grouped_shape_kernel<BF, BIG, INL, 2, 1>;
+          case Route::kGroupedSmall: return (const void*)&rgcn_grouped_small_kernel<BF, BIG, INL>;
+          case Route::kGroupedF32: return (const void*)&rgcn_grouped_f32_kernel<BIG, INL>;
+          case Route::kGroupedF32Small: return (const void*)&rgcn_grouped_f32_small_kernel<BIG, INL>;
+          default: return nullptr;
+        }
+      });
+    });
+  });
+}
+
+// pyg_hip_rgcn_last_route(): the plan of the last launch on this thread (named when asked for, not on every launch)
+thread_local RgcnPlan g_last_plan;
+
+// ---- the relation records ----------------------------------------------------------------------------------------------------
+// The device records of a call into `hr`.  Returns `big`: some feature table is 4 GB or more, so that a row's byte offset needs
+// 64 bits (for the atomic kernel's 256-byte rows that is a table of 2^24 rows or more).
+bool fill_relations(const pyg_hip_rgcn_relation* rels, int64_t R, const void* x, int64_t num_x_rows, int64_t row_bytes, RelDev* hr) {
+  bool big = false;
+  for (int64_t r = 0; r < R; ++r) {
+    hr[r].gather_index = rels[r].gather_index;
+    hr[r].scatter_index = rels[r].scatter_index;
+    hr[r].weight = static_cast<const char*>(rels[r].weight);
+    hr[r].num_edges = rels[r].num_edges;
+    hr[r].gather_offset = rels[r].gather_offset;
+    hr[r].scatter_offset = rels[r].scatter_offset;
+    hr[r].x = static_cast<const char*>(rels[r].x ? rels[r].x : x);
+    hr[r].gather_map = rels[r].gather_map;
+    hr[r].x_rows = rels[r].x ? rels[r].x_rows : num_x_rows;
+    hr[r].map_len = rels[r].gather_map_len;
+    big = big || hr[r].x_rows * row_bytes >= (1LL << 32);
+  }
+  return big;
+}
+
+// Where the records and the mode's vectors (`bytes` in all: the front of the workspace) are written on the host.  inl: *staged =
+// nullptr, they are the descriptor's own arrays and travel in the kernel argument -- staging them through pinned memory put a
+// host-to-device copy in front of every launch of a 50 us kernel.  Otherwise a pinned block that stage_commit copies over.
+int stage_begin(bool inl, size_t bytes, char** staged) {
+  void* p = nullptr;
+  if (!inl) {
+    int rc = pinned_stage().acquire(bytes, &p);
+    if (rc != PYG_HIP_OK) return rc;
+  }
+  *staged = static_cast<char*>(p);
+  return PYG_HIP_OK;
+}
+
+int stage_commit(const char* staged, size_t bytes, void* workspace, hipStream_t stream) {
+  if (!staged) return PYG_HIP_OK;
+  PYG_HIP_CHECK(hipMemcpyAsync(workspace, staged, bytes, hipMemcpyHostToDevice, stream));
+  return pinned_stage().commit(stream);
+}
+
+// ---- the workspaces: offsets of every region, for the size queries and the launchers alike -------------------------------------
+struct AtomicWs {
+  size_t tiles;   // [R + 1] tile prefix, behind the records at 0
+  size_t err;     // the error word of PYG_HIP_RGCN_CHECKED; [0, err) is what a staged call copies
+  size_t bytes;
+};
+AtomicWs carve_atomic(int64_t R) {
+  AtomicWs w;
+  w.tiles = align_up(sizeof(RelDev) * (size_t)std::max<int64_t>(R, 1), 256);
+  w.err = w.tiles + align_up(sizeof(int32_t) * (size_t)(R + 1), 256);
+  w.bytes = w.err + 256;
+  return w;
+}
+
+struct GroupedWs {
+  size_t vecs;        // eprefix [R + 1], rp_off [R], span [R], behind the records at 0
+  size_t meta;        // [2 R] first and last scatter index of every relation; [0, meta) is what a staged call copies
+  size_t err;         // the error word of PYG_HIP_RGCN_CHECKED
+  size_t long_rows;   // the call id, if some row has more than 16 edges
+  size_t rp;          // [rp_entries] row starts
+  size_t dbg;         // (PYG_ABL_ & 16: the last 64 KB)
+  size_t bytes;
+};
+GroupedWs carve_grouped(int64_t R, size_t rp_entries) {
+  const size_t Rz = (size_t)std::max<int64_t>(R, 1);
+  GroupedWs w;
+  w.vecs = align_up(sizeof(RelDev) * Rz, 256);
+  w.meta = w.vecs + align_up(sizeof(int64_t) * (3 * Rz + 1), 256);
+  w.err = w.meta + align_up(sizeof(int32_t) * 2 * Rz, 256);
+  w.long_rows = w.err + 64;
+  w.rp = w.err + 256;
+  w.dbg = w.rp + align_up(sizeof(int32_t) * rp_entries, 256);
+  w.bytes = w.dbg + ((PYG_ABL_ & 16) ? 65536 : 0);
+  return w;
+}
+size_t grouped_rp_entries(const pyg_hip_rgcn_relation* rels, int64_t R, int64_t out_rows) {
+  size_t rp = 0;
+  for (int64_t r = 0; r < R; ++r) rp += (size_t)grouped_span(rels[r], out_rows);
+  return rp;
+}
+
+// ---- the error protocol ------------------------------------------------------------------------------------------------------
 const char* rgcn_error_text(int code) {
   return code == 1 ? "a gather index out of range" : code == 2 ? "a scatter index out of range"
                                                                 : "scatter indices that are not grouped (nondecreasing) although PYG_HIP_RGCN_GROUPED promised so";
 }
 
+// PYG_HIP_RGCN_CHECKED: the kernels leave the code in a word of the workspace, finish() waits for the stream and reads it -- the
+// caller asked for a verdict.  PYG_HIP_RGCN_DEFERRED (ignored with _CHECKED): validated without a synchronisation -- offenders are
+// redirected to row 0 or dropped (never an out-of-bounds access) and the kernels leave the code in a pinned word of this device;
+// whoever looks next -- begin() of the next call here, or pyg_hip_rgcn_pending_error -- reports it.  Neither: no check.
+struct ErrorCheck {
+  bool sync = false, deferred = false;
+  int* word = nullptr;   // what the kernels write
+  bool on() const { return sync || deferred; }
+
+  int begin(int flags, int* ws_word, hipStream_t stream) {
+    sync = (flags & PYG_HIP_RGCN_CHECKED) != 0;
+    deferred = !sync && (flags & PYG_HIP_RGCN_DEFERRED) != 0;
+    word = ws_word;
+    if (sync) PYG_HIP_CHECK(hipMemsetAsync(word, 0, sizeof(int), stream));
+    if (deferred) {
+      int rc = deferred_error_slot(&word);
+      if (rc != PYG_HIP_OK) return rc;
+      const int pending = *static_cast<volatile int*>(word);
+      if (pending != 0) {
+        *static_cast<volatile int*>(word) = 0;
+        return fail(PYG_HIP_ERR_INVALID,
+                    "rgcn_fused: an earlier call on this device had %s (out-of-range edges were redirected to row 0 or "
+                    "dropped; set PYG_HIP_RGCN_CHECK=1 to fail in the call that has them)",
+                    rgcn_error_text(pending));
+      }
+    }
+    return PYG_HIP_OK;
+  }
+
+  int finish(hipStream_t stream) {
+    if (sync) {
+      int host_err = 0;
+      PYG_HIP_CHECK(hipMemcpyAsync(&host_err, word, sizeof(int), hipMemcpyDeviceToHost, stream));
+      PYG_HIP_CHECK(hipStreamSynchronize(stream));
+      if (host_err != 0) return fail(PYG_HIP_ERR_INVALID, "rgcn_fused: the call has %s", rgcn_error_text(host_err));
+    }
+    PYG_HIP_CHECK(hipGetLastError());
+    return PYG_HIP_OK;
+  }
+};
+
+// ---- the launchers -----------------------------------------------------------------------------------------------------------
+// The atomic kernel: `out` is ACCUMULATED into.  `tiles`: 128-edge tiles of all relations.
+int rgcn_atomic_launch(int dtype, const void* x, int64_t num_x_rows, const pyg_hip_rgcn_relation* rels, int64_t R, void* out,
+                       int64_t num_out_rows, int64_t tiles, int flags, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  PYG_HIP_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "rgcn_fused: misaligned tensor");
+  PYG_HIP_REQUIRE(tiles < (1LL << 31), "rgcn_fused: too many tiles");
+  const AtomicWs lay = carve_atomic(R);
+  if (workspace == nullptr || workspace_bytes < lay.bytes)
+    return fail(PYG_HIP_ERR_WORKSPACE, "rgcn_fused: workspace of %zu bytes needed, got %zu", lay.bytes, workspace_bytes);
+  RgcnPlan plan = rgcn_plan(Route::kAtomic, dtype, 128, 128, R);
+  RgcnDesc desc;
+  ::memset(&desc, 0, sizeof(desc));
+  char* staged = nullptr;
+  if (int rc = stage_begin(plan.inl, lay.err, &staged)) return rc;
+  RelDev* hr = staged ? reinterpret_cast<RelDev*>(staged) : desc.irels;
+  int32_t* ht = staged ? reinterpret_cast<int32_t*>(staged + lay.tiles) : desc.itile;
+  plan.big = fill_relations(rels, R, x, num_x_rows, 256, hr);
+  int64_t t = 0;
+  for (int64_t r = 0; r < R; ++r) {
+    ht[r] = (int32_t)t;
+    t += (rels[r].num_edges + 127) / 128;
+  }
+  ht[R] = (int32_t)t;
+  if (int rc = stage_commit(staged, lay.err, workspace, stream)) return rc;
+  char* w = static_cast<char*>(workspace);
+  if (staged) {
+    desc.rels = reinterpret_cast<const RelDev*>(w);
+    desc.tile_start = reinterpret_cast<const int32_t*>(w + lay.tiles);
+  }
+  const bool cas = (flags & PYG_HIP_RGCN_CAS) != 0 || float_atomic_mode() == 1;
+  ErrorCheck err;
+  if (int rc = err.begin(flags, reinterpret_cast<int*>(w + lay.err), stream)) return rc;
+  plan.ck = err.on();
+  plan.kern = rgcn_kernel(plan);
+  if (int rc = ensure_dynamic_lds(plan.kern, plan.lds)) return rc;
+  // persistent grid: every workgroup a contiguous range of >= 2 tiles
+  int64_t per_cu = plan.per_cu;
+  int64_t min_tiles = 2;
+  int dbg = 0;
+#ifdef PYG_HIP_EXPERIMENTS  // timing ablations: never part of the shipped library
+  if (const char* e = getenv("PYG_HIP_RGCN_WGS")) per_cu = std::max(1, atoi(e));
+  if (const char* e = getenv("PYG_HIP_RGCN_MIN_TILES")) min_tiles = std::max(1, atoi(e));
+  if (const char* e = getenv("PYG_HIP_RGCN_DBG")) dbg = atoi(e);
+#endif
+  if (cas) dbg |= 32;
+  note_accumulate("pyg_hip_rgcn_fused", out, (size_t)num_out_rows * 256, "the caller (`out` is accumulated into)", stream, cas ? 1 : 0);
+  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((tiles + min_tiles - 1) / min_tiles, per_cu * (int64_t)device_info().num_cus));
+  char* outc = static_cast<char*>(out);
+  int Ri = (int)R;
+  void* args[] = {(void*)&desc, (void*)&Ri, (void*)&outc, (void*)&num_out_rows, (void*)&err.word, (void*)&dbg};
+  PYG_HIP_CHECK(hipLaunchKernel(plan.kern, dim3((unsigned)grid), dim3(256), args, plan.lds, stream));
+  g_last_plan = plan;
+  return err.finish(stream);
+}
+
 // PYG_HIP_RGCN_GROUPED: the row-start launch, then the owner-computes kernel (rgcn_grouped.h).  `out` is WRITTEN.
 int rgcn_grouped_launch(int dtype, const void* x, int64_t num_x_rows, const pyg_hip_rgcn_relation* rels, int64_t R, void* out,
-                        int64_t num_out_rows, int64_t K, int64_t M, int checked, void* workspace, size_t workspace_bytes,
+                        int64_t num_out_rows, int64_t K, int64_t M, int flags, void* workspace, size_t workspace_bytes,
                         hipStream_t stream) {
   const size_t esz = dtype == PYG_F32 ? 4 : 2;
-  // 16-bit: K, M both in {128, 256} have their own instances; every other pair of multiples of 8 up to 256 takes the instance
-  // with run-time row sizes (rgcn_grouped_small_kernel: KC = MC = 2 slices, those that do not exist skipped)
-  const bool small = esz == 2 && !((K == 128 || K == 256) && (M == 128 || M == 256));
-  const int KC = small ? 2 : (int)(K * esz / 256), MC = small ? 2 : (int)(M * esz / 256);   // 256-byte slices of a feature row / of a row of `out`
   if (num_out_rows == 0) return PYG_HIP_OK;
   PYG_HIP_REQUIRE(out, "rgcn_fused: NULL tensor");
   PYG_HIP_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "rgcn_fused: 'out' must be 16-byte aligned in grouped mode");
   if (num_out_rows >= (1LL << 31) - 64)
     return fail(PYG_HIP_ERR_UNSUPPORTED, "rgcn_fused: grouped mode handles fewer than 2^31 output rows");
-  if (R > kGroupedMaxRel)
+  const Route route = choose_rgcn_route(dtype, K, M, R, flags);
+  if (route == Route::kUnsupported)   // (the type and the shape have passed shape_route)
     return fail(PYG_HIP_ERR_UNSUPPORTED, "rgcn_fused: grouped mode handles up to %d relations", kGroupedMaxRel);
   int64_t E = 0;
   for (int64_t r = 0; r < R; ++r) {
@@ -497,67 +770,42 @@ int rgcn_grouped_launch(int dtype, const void* x, int64_t num_x_rows, const pyg_
     PYG_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)num_out_rows * (size_t)M * esz, stream));
     return PYG_HIP_OK;
   }
-  const size_t need = grouped_workspace_bytes(rels, R, num_out_rows);
-  if (workspace == nullptr || workspace_bytes < need)
+  const GroupedWs lay = carve_grouped(R, grouped_rp_entries(rels, R, num_out_rows));
+  if (workspace == nullptr || workspace_bytes < lay.bytes)
     return fail(PYG_HIP_ERR_WORKSPACE, "rgcn_fused: grouped mode needs a workspace of %zu bytes (pyg_hip_rgcn_grouped_workspace_size), got %zu",
-                need, workspace_bytes);
-  const size_t rel_b = align_up(sizeof(RelDev) * (size_t)R, 256);
-  const size_t vec_b = align_up(sizeof(int64_t) * (size_t)(3 * R + 1), 256);
-  const size_t meta_b = align_up(sizeof(int32_t) * 2 * (size_t)R, 256);
-  const bool inl = R <= kRgcnInline;
+                lay.bytes, workspace_bytes);
+  RgcnPlan plan = rgcn_plan(route, dtype, K, M, R);
   GroupedDesc desc;
   ::memset(&desc, 0, sizeof(desc));
-  RelDev* hr = desc.irels;
-  int64_t* hp = desc.ieprefix;
-  int64_t* ho = desc.irp_off;
-  int64_t* hs = desc.ispan;
-  if (!inl) {
-    void* staged = nullptr;
-    int rc = pinned_stage().acquire(rel_b + vec_b, &staged);
-    if (rc != PYG_HIP_OK) return rc;
-    hr = static_cast<RelDev*>(staged);
-    hp = reinterpret_cast<int64_t*>(static_cast<char*>(staged) + rel_b);
-    ho = hp + (R + 1);
-    hs = ho + R;
-  }
-  bool big = false;
+  char* staged = nullptr;
+  if (int rc = stage_begin(plan.inl, lay.meta, &staged)) return rc;
+  RelDev* hr = staged ? reinterpret_cast<RelDev*>(staged) : desc.irels;
+  int64_t* hp = staged ? reinterpret_cast<int64_t*>(staged + lay.vecs) : desc.ieprefix;
+  int64_t* ho = staged ? hp + (R + 1) : desc.irp_off;
+  int64_t* hs = staged ? ho + R : desc.ispan;
+  plan.big = fill_relations(rels, R, x, num_x_rows, (int64_t)(K * esz), hr);
   int64_t e = 0, rp_entries = 0;
   for (int64_t r = 0; r < R; ++r) {
-    hr[r].gather_index = rels[r].gather_index;
-    hr[r].scatter_index = rels[r].scatter_index;
-    hr[r].weight = static_cast<const char*>(rels[r].weight);
-    hr[r].num_edges = rels[r].num_edges;
-    hr[r].gather_offset = rels[r].gather_offset;
-    hr[r].scatter_offset = rels[r].scatter_offset;
-    hr[r].x = static_cast<const char*>(rels[r].x ? rels[r].x : x);
-    hr[r].gather_map = rels[r].gather_map;
-    hr[r].x_rows = rels[r].x ? rels[r].x_rows : num_x_rows;
-    hr[r].map_len = rels[r].gather_map_len;
-    big = big || hr[r].x_rows * (int64_t)(K * esz) >= (1LL << 32);
     hp[r] = e;
     e += rels[r].num_edges;
-    const int64_t span = grouped_span(rels[r], num_out_rows);
     ho[r] = rp_entries;
-    hs[r] = span;
-    rp_entries += span;
+    hs[r] = grouped_span(rels[r], num_out_rows);
+    rp_entries += hs[r];
   }
   hp[R] = e;
+  if (int rc = stage_commit(staged, lay.meta, workspace, stream)) return rc;
   char* w = static_cast<char*>(workspace);
-  if (!inl) {
-    PYG_HIP_CHECK(hipMemcpyAsync(w, hr, rel_b + vec_b, hipMemcpyHostToDevice, stream));
-    int rc = pinned_stage().commit(stream);
-    if (rc != PYG_HIP_OK) return rc;
+  if (staged) {
     desc.rels = reinterpret_cast<const RelDev*>(w);
-    desc.eprefix = reinterpret_cast<const int64_t*>(w + rel_b);
+    desc.eprefix = reinterpret_cast<const int64_t*>(w + lay.vecs);
     desc.rp_off = desc.eprefix + (R + 1);
     desc.span = desc.rp_off + R;
   }
-  desc.meta = reinterpret_cast<int32_t*>(w + rel_b + vec_b);
-  int* err_dev = reinterpret_cast<int*>(w + rel_b + vec_b + meta_b);
-  desc.rp = reinterpret_cast<int32_t*>(w + rel_b + vec_b + meta_b + 256);
-  desc.long_rows = reinterpret_cast<uint64_t*>(w + rel_b + vec_b + meta_b + 64);
+  desc.meta = reinterpret_cast<int32_t*>(w + lay.meta);
+  desc.rp = reinterpret_cast<int32_t*>(w + lay.rp);
+  desc.long_rows = reinterpret_cast<uint64_t*>(w + lay.long_rows);
 #if PYG_ABL_ & 16
-  desc.dbg = reinterpret_cast<uint64_t*>(w + need - 65536);
+  desc.dbg = reinterpret_cast<uint64_t*>(w + lay.dbg);
 #endif
   desc.row_bytes = (int)(K * esz);
   desc.out_bytes = (int)(M * esz);
@@ -566,84 +814,30 @@ int rgcn_grouped_launch(int dtype, const void* x, int64_t num_x_rows, const pyg_
     static const uint64_t salt = (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() << 24;
     desc.call_id = (salt ^ 0x9e3779b97f4a7c15ull) + counter.fetch_add(1) + 1;
   }
-  const bool deferred = (checked & PYG_HIP_RGCN_DEFERRED) != 0 && (checked & PYG_HIP_RGCN_CHECKED) == 0;
-  const bool sync_check = (checked & PYG_HIP_RGCN_CHECKED) != 0;
-  if (sync_check) PYG_HIP_CHECK(hipMemsetAsync(err_dev, 0, sizeof(int), stream));
-  if (deferred) {
-    int* slot = nullptr;
-    int rc = deferred_error_slot(&slot);
-    if (rc != PYG_HIP_OK) return rc;
-    const int pending = *static_cast<volatile int*>(slot);
-    if (pending != 0) {
-      *static_cast<volatile int*>(slot) = 0;
-      return fail(PYG_HIP_ERR_INVALID,
-                  "rgcn_fused: an earlier call on this device had %s (set PYG_HIP_RGCN_CHECK=1 to fail in the call that has them)",
-                  rgcn_error_text(pending));
-    }
-    err_dev = slot;
-  }
-  const bool bf = dtype == PYG_BF16, ck = sync_check || deferred;
-  const void* prep = ck ? (inl ? (const void*)&rgcn_rowstart_kernel<true, true> : (const void*)&rgcn_rowstart_kernel<true, false>)
-                        : (inl ? (const void*)&rgcn_rowstart_kernel<false, true> : (const void*)&rgcn_rowstart_kernel<false, false>);
-  const void* kern;
-  {
-#define PYG_RGCN_GPICK(K, BF, CK, BG) (inl ? (const void*)&K<BF, CK, BG, true> : (const void*)&K<BF, CK, BG, false>)
-#define PYG_RGCN_GPICK4(K)                                                                                                       \
-  (bf ? (ck ? (big ? PYG_RGCN_GPICK(K, true, true, true) : PYG_RGCN_GPICK(K, true, true, false))                                \
-            : (big ? PYG_RGCN_GPICK(K, true, false, true) : PYG_RGCN_GPICK(K, true, false, false)))                              \
-      : (ck ? (big ? PYG_RGCN_GPICK(K, false, true, true) : PYG_RGCN_GPICK(K, false, true, false))                              \
-            : (big ? PYG_RGCN_GPICK(K, false, false, true) : PYG_RGCN_GPICK(K, false, false, false))))
-    kern = PYG_RGCN_GPICK4(rgcn_grouped_kernel);
-#define PYG_RGCN_SPICK(KC_, MC_)                                                                                                        \
-  (bf ? (big ? (inl ? (const void*)&rgcn_grouped_shape_kernel<true, true, true, KC_, MC_> : (const void*)&rgcn_grouped_shape_kernel<true, true, false, KC_, MC_>)    \
-             : (inl ? (const void*)&rgcn_grouped_shape_kernel<true, false, true, KC_, MC_> : (const void*)&rgcn_grouped_shape_kernel<true, false, false, KC_, MC_>)) \
-      : (big ? (inl ? (const void*)&rgcn_grouped_shape_kernel<false, true, true, KC_, MC_> : (const void*)&rgcn_grouped_shape_kernel<false, true, false, KC_, MC_>)  \
-             : (inl ? (const void*)&rgcn_grouped_shape_kernel<false, false, true, KC_, MC_> : (const void*)&rgcn_grouped_shape_kernel<false, false, false, KC_, MC_>)))
-    if (small)
-      kern = bf ? (big ? (inl ? (const void*)&rgcn_grouped_small_kernel<true, true, true> : (const void*)&rgcn_grouped_small_kernel<true, true, false>)
-                       : (inl ? (const void*)&rgcn_grouped_small_kernel<true, false, true> : (const void*)&rgcn_grouped_small_kernel<true, false, false>))
-                : (big ? (inl ? (const void*)&rgcn_grouped_small_kernel<false, true, true> : (const void*)&rgcn_grouped_small_kernel<false, true, false>)
-                       : (inl ? (const void*)&rgcn_grouped_small_kernel<false, false, true> : (const void*)&rgcn_grouped_small_kernel<false, false, false>));
-    else if (dtype == PYG_F32 && (K != 128 || M != 128))
-      kern = big ? (inl ? (const void*)&rgcn_grouped_f32_small_kernel<true, true> : (const void*)&rgcn_grouped_f32_small_kernel<true, false>)
-                 : (inl ? (const void*)&rgcn_grouped_f32_small_kernel<false, true> : (const void*)&rgcn_grouped_f32_small_kernel<false, false>);
-    else if (dtype == PYG_F32)
-      kern = big ? (inl ? (const void*)&rgcn_grouped_f32_kernel<true, true> : (const void*)&rgcn_grouped_f32_kernel<true, false>)
-                 : (inl ? (const void*)&rgcn_grouped_f32_kernel<false, true> : (const void*)&rgcn_grouped_f32_kernel<false, false>);
-    else if (KC == 2 && MC == 2) kern = PYG_RGCN_SPICK(2, 2);
-    else if (KC == 1 && MC == 2) kern = PYG_RGCN_SPICK(1, 2);
-    else if (KC == 2 && MC == 1) kern = PYG_RGCN_SPICK(2, 1);
-#undef PYG_RGCN_SPICK
-#undef PYG_RGCN_GPICK4
-#undef PYG_RGCN_GPICK
-  }
-  // 16-bit: 32 KB of W, 32-row A tiles, three workgroups per CU; fp32: all 64 KB of W, an A tile of 16 rows of 528 bytes, two
-  // workgroups per CU (rgcn_grouped.h)
-  const bool wide = dtype == PYG_F32;
-  const int lds = (wide ? 65536 + 8704 : 32768 + 8192 * KC) + 2 * 4 * kGroupedMaxRel;
-  if (int rc_ = ensure_dynamic_lds(kern, lds)) return rc_;
+  ErrorCheck err;
+  if (int rc = err.begin(flags, reinterpret_cast<int*>(w + lay.err), stream)) return rc;
+  plan.ck = err.on();
+  plan.kern = rgcn_kernel(plan);
+  const void* prep = with_bool(plan.ck, [&](auto ck) {
+    return with_bool(plan.inl, [](auto in) { return (const void*)&rgcn_rowstart_kernel<decltype(ck)::value, decltype(in)::value>; });
+  });
+  if (int rc = ensure_dynamic_lds(plan.kern, plan.lds)) return rc;
   int Ri = (int)R;
   {
-    void* args[] = {(void*)&desc, (void*)&Ri, (void*)&err_dev};
+    void* args[] = {(void*)&desc, (void*)&Ri, (void*)&err.word};
     PYG_HIP_CHECK(hipLaunchKernel(prep, dim3((unsigned)((E + 255) / 256)), dim3(256), args, 0, stream));
   }
   {
     char* outc = static_cast<char*>(out);
-    void* args[] = {(void*)&desc, (void*)&Ri, (void*)&outc, (void*)&num_out_rows, (void*)&err_dev};
-    // persistent: three workgroups of 256 threads per CU (<= 168 VGPRs, 44 KB of LDS), blocks of 16 rows dealt round-robin (the rows with
-    // edges are the first ones of every node type: neighbours in the grid, spread over the chip)
+    void* args[] = {(void*)&desc, (void*)&Ri, (void*)&outc, (void*)&num_out_rows, (void*)&err.word};
+    // persistent: blocks of 16 rows dealt round-robin (the rows with edges are the first ones of every node type: neighbours in
+    // the grid, spread over the chip)
     const int64_t nblocks = (num_out_rows + 15) / 16;
-    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(nblocks, (wide ? 2 : 3) * (int64_t)device_info().num_cus));
-    PYG_HIP_CHECK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(256), args, lds, stream));
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(nblocks, plan.per_cu * (int64_t)device_info().num_cus));
+    PYG_HIP_CHECK(hipLaunchKernel(plan.kern, dim3((unsigned)grid), dim3(256), args, plan.lds, stream));
   }
-  if (sync_check) {
-    int host_err = 0;
-    PYG_HIP_CHECK(hipMemcpyAsync(&host_err, err_dev, sizeof(int), hipMemcpyDeviceToHost, stream));
-    PYG_HIP_CHECK(hipStreamSynchronize(stream));
-    if (host_err != 0) return fail(PYG_HIP_ERR_INVALID, "rgcn_fused: the call has %s", rgcn_error_text(host_err));
-  }
-  PYG_HIP_CHECK(hipGetLastError());
-  return PYG_HIP_OK;
+  g_last_plan = plan;
+  return err.finish(stream);
 }
 
 }  // namespace
@@ -661,16 +855,27 @@ int pyg_hip_rgcn_pending_error(void) {
   return pending;
 }
 
+int pyg_hip_rgcn_route(int dtype, int64_t K, int64_t M, int64_t R, int flags) { return (int)choose_rgcn_route(dtype, K, M, R, flags); }
+
+const char* pyg_hip_rgcn_last_route(void) {
+  static const char* const kFamilies[] = {"none", "atomic", "grouped_128", "grouped_shape", "grouped_small", "grouped_f32", "grouped_f32_small"};
+  thread_local char name[96];
+  const RgcnPlan& p = g_last_plan;
+  if (p.route == Route::kUnsupported) return "none";
+  snprintf(name, sizeof(name), "%s kc%d mc%d %s %s %s %s", kFamilies[(int)p.route], p.KC, p.MC,
+           p.dtype == PYG_BF16 ? "bf16" : p.dtype == PYG_F16 ? "f16" : "f32", p.ck ? "check" : "nocheck", p.big ? "big" : "nobig",
+           p.inl ? "inline" : "staged");
+  return name;
+}
+
 size_t pyg_hip_rgcn_grouped_workspace_size(const pyg_hip_rgcn_relation* relations, int64_t num_relations, int64_t num_out_rows) {
   if (relations == nullptr || num_relations <= 0 || num_out_rows <= 0) return 256;
-  return grouped_workspace_bytes(relations, num_relations, num_out_rows);
+  return carve_grouped(num_relations, grouped_rp_entries(relations, num_relations, num_out_rows)).bytes;
 }
 
 size_t pyg_hip_rgcn_fused_workspace_size(int64_t num_relations, int64_t num_edges) {
-  if (num_relations < 0) num_relations = 0;
   (void)num_edges;
-  return align_up(sizeof(RelDev) * (size_t)std::max<int64_t>(num_relations, 1), 256) +
-         align_up(sizeof(int32_t) * (size_t)(num_relations + 1), 256) + 256;
+  return carve_atomic(std::max<int64_t>(num_relations, 0)).bytes;
 }
 
 int pyg_hip_rgcn_fused(int dtype, const void* x, int64_t num_x_rows, const pyg_hip_rgcn_relation* rels, int64_t R,
@@ -680,9 +885,7 @@ int pyg_hip_rgcn_fused(int dtype, const void* x, int64_t num_x_rows, const pyg_h
   const bool grouped = (checked & PYG_HIP_RGCN_GROUPED) != 0;
   PYG_HIP_REQUIRE(dtype == PYG_BF16 || dtype == PYG_F16 || (grouped && dtype == PYG_F32),
                   "rgcn_fused: bfloat16 / float16 only (PYG_HIP_RGCN_GROUPED: float32 too)");
-  const bool any8 = K >= 8 && K <= 256 && M >= 8 && M <= 256 && K % 8 == 0 && M % 8 == 0;
-  const bool any4 = K >= 4 && K <= 128 && M >= 4 && M <= 128 && K % 4 == 0 && M % 4 == 0;   // (fp32: rows of multiples of 16 bytes up to 512)
-  if (dtype == PYG_F32 ? !any4 : (grouped ? !any8 : (K != 128 || M != 128)))
+  if (shape_route(dtype, K, M, grouped) == Route::kUnsupported)
     return fail(PYG_HIP_ERR_UNSUPPORTED,
                 "rgcn_fused: K = M = 128 only (PYG_HIP_RGCN_GROUPED: K, M any multiples of 8 up to 256 for the 16-bit types, of 4 up to 128 for float32); got %lld x %lld",
                 (long long)K, (long long)M);
@@ -712,112 +915,7 @@ int pyg_hip_rgcn_fused(int dtype, const void* x, int64_t num_x_rows, const pyg_h
   }
   if (grouped)
     return rgcn_grouped_launch(dtype, x, num_x_rows, rels, R, out, num_out_rows, K, M, checked, workspace, workspace_bytes, stream);
-  PYG_HIP_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "rgcn_fused: misaligned tensor");
-  PYG_HIP_REQUIRE(tiles < (1LL << 31), "rgcn_fused: too many tiles");
-  if (workspace == nullptr || workspace_bytes < pyg_hip_rgcn_fused_workspace_size(R, E))
-    return fail(PYG_HIP_ERR_WORKSPACE, "rgcn_fused: workspace of %zu bytes needed, got %zu",
-                pyg_hip_rgcn_fused_workspace_size(R, E), workspace_bytes);
-  const size_t rel_b = align_up(sizeof(RelDev) * (size_t)R, 256);
-  const size_t tile_b = align_up(sizeof(int32_t) * (size_t)(R + 1), 256);
-  const bool inl = R <= kRgcnInline;
-  RgcnDesc desc;
-  ::memset(&desc, 0, sizeof(desc));
-  RelDev* hr = desc.irels;
-  int32_t* ht = desc.itile;
-  if (!inl) {
-    void* staged = nullptr;
-    int rc = pinned_stage().acquire(rel_b + tile_b, &staged);
-    if (rc != PYG_HIP_OK) return rc;
-    hr = static_cast<RelDev*>(staged);
-    ht = reinterpret_cast<int32_t*>(static_cast<char*>(staged) + rel_b);
-  }
-  int64_t t = 0;
-  bool big = false;  // a feature table of 4 GB or more: 64-bit row offsets
-  for (int64_t r = 0; r < R; ++r) {
-    hr[r].gather_index = rels[r].gather_index;
-    hr[r].scatter_index = rels[r].scatter_index;
-    hr[r].weight = static_cast<const char*>(rels[r].weight);
-    hr[r].num_edges = rels[r].num_edges;
-    hr[r].gather_offset = rels[r].gather_offset;
-    hr[r].scatter_offset = rels[r].scatter_offset;
-    hr[r].x = static_cast<const char*>(rels[r].x ? rels[r].x : x);
-    hr[r].gather_map = rels[r].gather_map;
-    hr[r].x_rows = rels[r].x ? rels[r].x_rows : num_x_rows;
-    hr[r].map_len = rels[r].gather_map_len;
-    big = big || hr[r].x_rows >= (1LL << 24);
-    ht[r] = (int32_t)t;
-    t += (rels[r].num_edges + 127) / 128;
-  }
-  ht[R] = (int32_t)t;
-  char* w = static_cast<char*>(workspace);
-  if (!inl) {
-    PYG_HIP_CHECK(hipMemcpyAsync(w, hr, rel_b + tile_b, hipMemcpyHostToDevice, stream));
-    int rc = pinned_stage().commit(stream);
-    if (rc != PYG_HIP_OK) return rc;
-    desc.rels = reinterpret_cast<const RelDev*>(w);
-    desc.tile_start = reinterpret_cast<const int32_t*>(w + rel_b);
-  }
-  constexpr int lds = 32768 + 4 * 8192;
-  int* err_dev = reinterpret_cast<int*>(w + rel_b + tile_b);
-  const bool cas = (checked & PYG_HIP_RGCN_CAS) != 0 || float_atomic_mode() == 1;
-  const bool deferred = (checked & PYG_HIP_RGCN_DEFERRED) != 0 && (checked & PYG_HIP_RGCN_CHECKED) == 0;
-  checked &= PYG_HIP_RGCN_CHECKED;
-  if (checked) PYG_HIP_CHECK(hipMemsetAsync(err_dev, 0, sizeof(int), stream));
-  if (deferred) {
-    // validated without a synchronisation: offenders are redirected to row 0 (never an out-of-bounds access) and the
-    // kernel leaves the code in a pinned word of this device; whoever looks next -- the next call here, or
-    // pyg_hip_rgcn_pending_error -- reports it
-    int* slot = nullptr;
-    int rc = deferred_error_slot(&slot);
-    if (rc != PYG_HIP_OK) return rc;
-    const int pending = *static_cast<volatile int*>(slot);
-    if (pending != 0) {
-      *static_cast<volatile int*>(slot) = 0;
-      return fail(PYG_HIP_ERR_INVALID,
-                  "rgcn_fused: an earlier call on this device had %s (out-of-range edges were redirected to row 0 or "
-                  "dropped; set PYG_HIP_RGCN_CHECK=1 to fail in the call that has them)",
-                  rgcn_error_text(pending));
-    }
-    err_dev = slot;
-  }
-  const void* kern;
-  {
-#define PYG_RGCN_PICK3(BF, CK, BG) (inl ? (const void*)&rgcn_fused_kernel<BF, CK, BG, true> : (const void*)&rgcn_fused_kernel<BF, CK, BG, false>)
-#define PYG_RGCN_PICK(BF, CK, BG) PYG_RGCN_PICK3(BF, CK, BG)
-    const bool bf = dtype == PYG_BF16, ck = checked != 0 || deferred;
-    kern = bf ? (ck ? (big ? PYG_RGCN_PICK(true, true, true) : PYG_RGCN_PICK(true, true, false))
-                    : (big ? PYG_RGCN_PICK(true, false, true) : PYG_RGCN_PICK(true, false, false)))
-              : (ck ? (big ? PYG_RGCN_PICK(false, true, true) : PYG_RGCN_PICK(false, true, false))
-                    : (big ? PYG_RGCN_PICK(false, false, true) : PYG_RGCN_PICK(false, false, false)));
-#undef PYG_RGCN_PICK
-#undef PYG_RGCN_PICK3
-  }
-  if (int rc_ = ensure_dynamic_lds(kern, lds)) return rc_;
-  // persistent grid: two workgroups per CU (64 KB of LDS each), every one a contiguous range of >= 2 tiles
-  int64_t per_cu = 2;
-  int64_t min_tiles = 2;
-  int dbg = 0;
-#ifdef PYG_HIP_EXPERIMENTS  // timing ablations: never part of the shipped library
-  if (const char* e = getenv("PYG_HIP_RGCN_WGS")) per_cu = std::max(1, atoi(e));
-  if (const char* e = getenv("PYG_HIP_RGCN_MIN_TILES")) min_tiles = std::max(1, atoi(e));
-  if (const char* e = getenv("PYG_HIP_RGCN_DBG")) dbg = atoi(e);
-#endif
-  if (cas) dbg |= 32;
-  note_accumulate("pyg_hip_rgcn_fused", out, (size_t)num_out_rows * 256, "the caller (`out` is accumulated into)", stream, cas ? 1 : 0);
-  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((tiles + min_tiles - 1) / min_tiles, per_cu * (int64_t)device_info().num_cus));
-  char* outc = static_cast<char*>(out);
-  int Ri = (int)R;
-  void* args[] = {(void*)&desc, (void*)&Ri, (void*)&outc, (void*)&num_out_rows, (void*)&err_dev, (void*)&dbg};
-  PYG_HIP_CHECK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(256), args, lds, stream));
-  if (checked) {  // checked mode synchronises: the caller asked for a verdict
-    int host_err = 0;
-    PYG_HIP_CHECK(hipMemcpyAsync(&host_err, err_dev, sizeof(int), hipMemcpyDeviceToHost, stream));
-    PYG_HIP_CHECK(hipStreamSynchronize(stream));
-    if (host_err == 1) return fail(PYG_HIP_ERR_INVALID, "rgcn_fused: gather index out of range");
-    if (host_err == 2) return fail(PYG_HIP_ERR_INVALID, "rgcn_fused: scatter index out of range");
-  }
-  PYG_HIP_CHECK(hipGetLastError());
-  return PYG_HIP_OK;
+  return rgcn_atomic_launch(dtype, x, num_x_rows, rels, R, out, num_out_rows, tiles, checked, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -832,11 +832,3 @@ inline int64_t grouped_span(const pyg_hip_rgcn_relation& rel, int64_t out_rows) 
   const int64_t span = rel.scatter_rows > 0 ? std::min(rel.scatter_rows, to_end) : to_end;
   return span > 0 ? span : 0;
 }
-
-size_t grouped_workspace_bytes(const pyg_hip_rgcn_relation* rels, int64_t R, int64_t out_rows) {
-  size_t rp = 0;
-  for (int64_t r = 0; r < R; ++r) rp += (size_t)grouped_span(rels[r], out_rows);
-  const size_t Rz = (size_t)std::max<int64_t>(R, 1);
-  return align_up(sizeof(RelDev) * Rz, 256) + align_up(sizeof(int64_t) * (3 * Rz + 1), 256) + align_up(sizeof(int32_t) * 2 * Rz, 256) + 256 +
-         align_up(sizeof(int32_t) * rp, 256) + ((PYG_ABL_ & 16) ? 65536 : 0);
-}

@@ -31,7 +31,7 @@ import torch
 from torch import Tensor
 from torch.autograd.function import once_differentiable
 
-from . import ops
+from . import _capi, ops
 
 EdgeType = Tuple[str, str, str]
 
@@ -46,7 +46,6 @@ def pending_index_error() -> int:
     make that call outside a HIP-graph capture, e.g. in the warm-up): an error of one call is reported by whichever
     fused call or ``pending_index_error()`` comes next on the device, from any thread or model.  Where errors must be
     attributed to their call, use ``PYG_HIP_RGCN_CHECK=1`` (synchronising, fails in the call that has the bad index)."""
-    from . import _capi
     return int(_capi.lib().pyg_hip_rgcn_pending_error())
 
 
@@ -58,6 +57,14 @@ def last_layer_path() -> str:
     scatter_sum), ``'atomic'`` (``pyg::rgcn_fused`` with packed atomics) or ``'grouped'`` (the atomic-free kernel).
     Diagnostics, like ``sampler.last_mode``."""
     return _last_path[0]
+
+
+def last_layer_route() -> str:
+    r"""Which kernel the last fused layer launch of this thread ran, as ``pyg_hip_rgcn_last_route`` names it (family, slices,
+    type, ``check``, ``big``, ``inline`` / ``staged``: include/pyg_hip.h); ``'chain'`` where :func:`last_layer_path` says so."""
+    if _last_path[0] in ('chain', 'none'):
+        return _last_path[0]
+    return _capi.lib().pyg_hip_rgcn_last_route().decode()
 
 
 def type_offsets(num_nodes: Dict[str, int], node_types: List[str]) -> Dict[str, int]:
@@ -190,7 +197,16 @@ def _dx_grouped() -> bool:
     return m == 'grouped' or (m != 'atomic' and torch.are_deterministic_algorithms_enabled())
 
 
-_GROUPED_MAX_RELATIONS = 512   # kGroupedMaxRel of csrc/hip/rgcn_grouped.h: the relations' row ranges live in LDS
+_ROUTE_ATOMIC, _FLAG_GROUPED = 1, 8   # PYG_HIP_RGCN_ROUTE_ATOMIC, PYG_HIP_RGCN_GROUPED
+
+
+def _route(x: Tensor, weight: Tensor, relations: int, grouped: bool) -> int:
+    # PYG_HIP_RGCN_ROUTE_* (0: unsupported) of a layer with features like `x`: the table of pyg_hip_rgcn_route in
+    # include/pyg_hip.h -- types, shapes and the relation count are decided there and nowhere else
+    code = _capi.DTYPES.get(x.dtype)
+    if x.dim() != 2 or weight.dim() != 3 or code is None:
+        return 0
+    return _capi.lib().pyg_hip_rgcn_route(code, x.size(1), weight.size(2), relations, _FLAG_GROUPED if grouped else 0)
 
 
 def _resolve_grouped(grouped: Optional[bool], scatter: List[Tensor]) -> bool:
@@ -199,24 +215,15 @@ def _resolve_grouped(grouped: Optional[bool], scatter: List[Tensor]) -> bool:
     if grouped is None:
         from . import sampler
         grouped = all(sampler.rows_are_grouped(s) for s in scatter)
-    return bool(grouped) and len(scatter) <= _GROUPED_MAX_RELATIONS
+    return bool(grouped)
 
 
-def _fusable(x: Tensor, weight: Tensor, grouped: bool = False) -> bool:
-    # the atomic kernel: 16-bit, F_in = F_out = 128; the grouped (atomic-free) kernel: 16-bit with F_in, F_out any multiples
-    # of 8 up to 256, or float32 with multiples of 4 up to 128
+def _fusable(x: Tensor, weight: Tensor, grouped: bool = False, relations: int = 0) -> bool:
+    # one device, one type, matching inner sizes -- and a kernel for the type, the shape and the relation count (_route)
     if x.dim() != 2 or weight.dim() != 3:
         return False
-    K, M = x.size(1), weight.size(2)
-    if not grouped:
-        shape_ok = K == 128 and M == 128
-    elif x.dtype == torch.float32:   # rows of multiples of 16 bytes up to 512
-        shape_ok = 4 <= K <= 128 and 4 <= M <= 128 and K % 4 == 0 and M % 4 == 0
-    else:
-        shape_ok = 8 <= K <= 256 and 8 <= M <= 256 and K % 8 == 0 and M % 8 == 0
-    dtypes = (torch.bfloat16, torch.float16, torch.float32) if grouped else (torch.bfloat16, torch.float16)
-    return (x.is_cuda and x.dtype in dtypes and shape_ok and weight.size(1) == K and weight.dtype == x.dtype and
-            weight.device == x.device)
+    return (x.is_cuda and weight.size(1) == x.size(1) and weight.dtype == x.dtype and weight.device == x.device and
+            _route(x, weight, relations, grouped) != 0)
 
 
 def _fresh_out(like: Tensor, rows: int, cols: int, grouped: bool) -> Tensor:
@@ -287,13 +294,12 @@ def _dx_scatter(grad_out: Tensor, weight: Tensor, gather: List[Tensor], scatter:
     E = sum(g.numel() for g in gather)
     if E == 0:
         return grad_out.new_zeros(rows, weight.size(1))
-    if _dx_grouped() and _fusable(grad_out, wt, True) and len(gather) <= _GROUPED_MAX_RELATIONS:
+    if _dx_grouped() and _fusable(grad_out, wt, True, len(gather)):
         g_sorted, s_perm = _transposed_sample(gather, scatter, rows)
         gx = grad_out.new_empty(rows, weight.size(1))   # (written once per row by the grouped kernel)
         torch.ops.pyg.rgcn_fused(grad_out, s_perm, g_sorted, soff, goff, wt, gx, True, grows)
         return gx
-    if torch.are_deterministic_algorithms_enabled() or weight.size(1) != 128 or weight.size(2) != 128 or \
-            weight.dtype == torch.float32:   # (the atomic kernel: 16-bit, 128 x 128)
+    if torch.are_deterministic_algorithms_enabled() or _route(grad_out, wt, len(gather), False) != _ROUTE_ATOMIC:
         ptr, gidx, sidx = _rel_ptr_and_indices(gather, scatter, goff, soff)
         msgs = ops.segment_matmul(ops.gather_coo(grad_out, sidx), ptr, wt)   # (the kernel takes any index order)
         return ops.scatter_sum(msgs, gidx, dim=0, dim_size=rows)
@@ -435,10 +441,12 @@ def rgcn_layer_fused(x: Tensor, offsets: Dict[str, int], row_dict: Dict[EdgeType
     ooff = out_offsets(offsets, num_out_rows)
     total = ooff['__total__']
     roles = [edge_roles(et, row_dict, col_dict, csc) for et in edge_types]
-    grouped = _resolve_grouped(grouped, [r[2] for r in roles])
+    # (a promised layer the grouped kernels do not take -- more relations than their row ranges have room for in LDS -- may
+    # still take the atomic kernel)
+    grouped = _resolve_grouped(grouped, [r[2] for r in roles]) and _fusable(x, weight, True, len(roles))
     # torch.use_deterministic_algorithms(True): the fused kernel adds with packed 16-bit atomics (order-dependent); the
     # three-op chain is atomic-free in that mode (gather, per-relation MFMA tiles, scatter_sum through a stable sort)
-    if not _fusable(x, weight, grouped) or (torch.are_deterministic_algorithms_enabled() and not grouped):
+    if not (grouped or _fusable(x, weight, False, len(roles))) or (torch.are_deterministic_algorithms_enabled() and not grouped):
         return rgcn_layer(x, offsets, row_dict, col_dict, edge_types, weight, csc, num_out_rows)
     gather, scatter = [r[0] for r in roles], [r[2] for r in roles]
     goff, soff = [offsets[r[1]] for r in roles], [ooff[r[3]] for r in roles]
@@ -470,19 +478,20 @@ def rgcn_layer_fused_tables(feat_dict: Dict[str, Tensor], node_id_dict: Dict[str
     off = type_offsets({t: node_id_dict[t].numel() for t in node_types}, node_types)
     ooff = out_offsets(off, num_out_rows)
     roles = [edge_roles(et, row_dict, col_dict, csc) for et in edge_types]
-    grouped = _resolve_grouped(grouped, [r[2] for r in roles])
     f0 = feat_dict[node_types[0]]
+    promised = _resolve_grouped(grouped, [r[2] for r in roles])
+    grouped = promised and _fusable(f0, weight, True, len(roles))
     feats = [feat_dict[t] for t in node_types]
     nids = [node_id_dict[t] for t in node_types]
     needs_grad = torch.is_grad_enabled() and (weight.requires_grad or any(f.requires_grad for f in feats))
     # every table and the weight: one device, one 16-bit type, F = 128 (anything else: the chain, which checks nothing
     # more than its own ops do)
-    ok = _fusable(f0, weight, grouped) and all(f.dim() == 2 and f.size(1) == f0.size(1) and f.dtype == f0.dtype and
+    ok = (grouped or _fusable(f0, weight, False, len(roles))) and all(f.dim() == 2 and f.size(1) == f0.size(1) and f.dtype == f0.dtype and
                                                f.device == f0.device for f in feats) and \
         all(n.device == f0.device and n.dtype == torch.long and n.dim() == 1 for n in nids)
     if not ok or (torch.are_deterministic_algorithms_enabled() and not grouped):   # (deterministic mode: see rgcn_layer_fused)
         x = torch.cat([feat_dict[t][node_id_dict[t]] for t in node_types])
-        return rgcn_layer_fused(x, off, row_dict, col_dict, edge_types, weight, csc, grouped, num_out_rows)
+        return rgcn_layer_fused(x, off, row_dict, col_dict, edge_types, weight, csc, promised, num_out_rows)
     tidx = {t: i for i, t in enumerate(node_types)}
     gather, scatter = [r[0] for r in roles], [r[2] for r in roles]
     gtype, soff = [tidx[r[1]] for r in roles], [ooff[r[3]] for r in roles]

@@ -194,6 +194,7 @@ def test_a_sampler_output_modified_in_place_takes_the_atomic_kernel_and_gives_th
     want = restate_csc(x, off, row_d, col_d, W)
     y = rgcn.rgcn_layer_fused(x, off, row_d, col_d, MAG_ETS, W, csc=True)
     assert 'pyg_hip_rgcn_fused' in diagnostics.last_accumulate_info() and rgcn.last_layer_path() == 'atomic'
+    assert rgcn.last_layer_route().startswith('atomic kc1 mc1 ')
     torch.cuda.synchronize()
     assert rgcn.pending_index_error() == 0
     assert torch.equal(y.double(), want)

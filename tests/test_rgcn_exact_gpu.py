@@ -79,6 +79,10 @@ def grouped_layer_bits(t, K, M, case, long_rows):
     W = c['Wi'].to(dtype).cuda()
     y = rgcn.rgcn_layer_fused(x, off, rows, cols, c['ets'], W, grouped=True)
     assert rgcn.last_layer_path() == 'grouped'
+    # the pipeline's shape and the run-time-size instance, by name (three relations: records in the kernel argument)
+    # (validation follows PYG_HIP_RGCN_CHECK of the environment, which this test does not fix)
+    route = ('grouped_128 kc1 mc1 ' if (K, M) == (128, 128) else 'grouped_small kc2 mc2 ') + t + ' check nobig inline'
+    assert rgcn.last_layer_route().replace('nocheck', 'check') == route
     assert y.dtype == dtype and y.shape == (off['__total__'], M)
     check(y, c, dtype, f'rgcn_layer_fused {t} {K} x {M} case {case}')
     # through the global tables and node ids
@@ -90,7 +94,7 @@ def grouped_layer_bits(t, K, M, case, long_rows):
         tab[k][nid[k]] = c['xi'][c['off'][k]:c['off'][k] + c['n'][k]]
     yt = rgcn.rgcn_layer_fused_tables({k: tab[k].to(dtype).cuda() for k in c['types']}, {k: nid[k].cuda() for k in c['types']},
                                       c['types'], rows, cols, c['ets'], W, grouped=True)
-    assert rgcn.last_layer_path() == 'grouped'
+    assert rgcn.last_layer_path() == 'grouped' and rgcn.last_layer_route().replace('nocheck', 'check') == route
     check(yt, c, dtype, f'rgcn_layer_fused_tables {t} {K} x {M} case {case}')
     torch.cuda.synchronize()
     assert rgcn.pending_index_error() == 0
