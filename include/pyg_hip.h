@@ -57,6 +57,8 @@ typedef enum {
 
 /* Version of THIS interface: bumped whenever a signature or the meaning of an argument changes, so that a caller built
  * against an older header can tell (pyg_hip_abi_version() != the PYG_HIP_ABI_VERSION it was compiled with).
+ *  21: pyg_hip_edge_lookup, pyg_hip_negative_sample (edge membership on a CSR graph and exact uniform draws over its
+ *      non-edges, keyed and deterministic).
  *  20: pyg_hip_rgcn_route, pyg_hip_rgcn_last_route (which kernel family serves a fused R-GCN call: asked without running,
  *      told after).
  *  19: pyg_hip_node2vec_walk (second-order (p, q) random walks, keyed and deterministic).
@@ -86,7 +88,7 @@ typedef enum {
  *      pyg_hip_sampler_table_cache_release; the weight-gradient workspace holds partial slabs instead of an fp32 image.
  *   4: round 4 -- `flags` in front of `stream` in pyg_hip_segment_matmul / pyg_hip_grouped_matmul, `index_sorted` of
  *      pyg_hip_scatter became a bit field, pyg_hip_matmul_set_schedule / _set_f32_split removed, fp32 default = IEEE MFMAs. */
-#define PYG_HIP_ABI_VERSION 20
+#define PYG_HIP_ABI_VERSION 21
 PYG_HIP_API int pyg_hip_abi_version(void);
 /* Replaces pyg::cuda_version (pyg_lib/csrc/library.cpp:19-29): returns the HIP runtime version
  * the library was built against (HIP_VERSION), never -1. */
@@ -703,6 +705,57 @@ PYG_HIP_API int pyg_hip_node2vec_walk(int index_dtype, const void* rowptr, int64
                                       int64_t num_edges, const void* seed, int64_t num_seeds, int64_t walk_length,
                                       float a_ret, float a_near, float a_far, uint64_t key, int max_attempts, void* out,
                                       void* stream);
+
+/*
+ * Edge lookup and negative sampling on a CSR graph (this build only; neither has an operator in the reference).  rowptr has
+ * num_src + 1 entries, col num_edges; destinations are ids in [0, num_dst).  index_dtype is PYG_I32 or PYG_I64 and types
+ * every buffer.  Both are pure functions of their arguments: the same on the device, on the binding's CPU key and in
+ * tests/_negative_ref.py, bit for bit; integer arithmetic only.  One lane per item; no atomics, no allocation, no
+ * synchronisation, no host read.
+ *
+ * Precondition.  col strictly ascending within each row (a coalesced graph).  On rows that break it every read stays in
+ * bounds, every result is -1 or lies in the candidate range and all three implementations still agree (they run the same
+ * loops); only "is not an edge" and uniformity are unspecified.  Every comparison below is meant in exact integers: the
+ * device and the host code arrange theirs so that nothing overflows int64 whatever rowptr, col and ptr hold (kth clamps
+ * W[mid] to [lo - 1, hi]; an empty range hi <= lo gives -1 before hi - lo is formed; the global bisection compares
+ * rowptr[s + 1] with (s + 1) * num_dst - R).
+ * A row is VALID if its source s lies in [0, num_src) and (rs, re) = (rowptr[s], rowptr[s+1]) has 0 <= rs <= re <= num_edges;
+ * then row = col[rs, re).
+ * lower_bound(W, x):  a = 0, b = |W|; while a < b: mid = (a + b) / 2; if W[mid] < x then a = mid + 1 else b = mid.  Result a.
+ * kth(W, lo, r):      a = 0, b = |W|; while a < b: mid = (a + b) / 2; if W[mid] - lo - mid > r then b = mid else a = mid + 1.
+ *                     Result lo + r + a: the r-th value of lo, lo + 1, ... that is not in W.
+ *
+ * pyg_hip_edge_lookup: out[q] = rs + lower_bound(row, dst[q]) if that position lies in the row and holds dst[q] -- the
+ * first entry of row src[q] that equals dst[q] -- else -1; -1 also if row src[q] is not valid.
+ *
+ * pyg_hip_negative_sample.  Words: item t owns at::Philox4_32(key, subsequence = t, offset = 0), takes its first two words
+ * and forms w = (w0 << 32) | w1; a draw below n is (w * n) >> 64, the high half of the 64 x 64 product (bias <= n / 2^64).
+ *  src != NULL (structured): out is [num_items, num_neg], item t = i * num_neg + j.  out[i][j] is a destination x with
+ *   (src[i], x) not an edge, x != src[i] if exclude_self, x in the graph of src[i] if ptr; -1 if there is none.
+ *   1. s = src[i]; -1 unless row s is valid.
+ *   2. [lo, hi) = [0, num_dst) without ptr.  With ptr (num_graphs + 1 entries): a = 0, b = num_graphs + 1; while a < b:
+ *      mid = (a + b) / 2; if ptr[mid] <= s then a = mid + 1 else b = mid.  g = a - 1; -1 if g < 0 or g >= num_graphs;
+ *      lo = max(ptr[g], 0), hi = min(ptr[g+1], num_dst).
+ *   3. W = row[lower_bound(row, lo), lower_bound(row, hi)), d = |W| (0 if the bounds are reversed).
+ *   4. self_ex = exclude_self && lo <= s < hi && s not in W (by lower_bound(W, s)).
+ *   5. n = (hi - lo) - d - self_ex; -1 if n <= 0.  r = the draw below n; x = kth(W, lo, r); if self_ex && x >= s then
+ *      x = kth(W, lo, r + 1).
+ *  src == NULL (global), whatever num_items is -- a structured call without sources has no items and needs no call:
+ *   num_items is ignored, out is [2, num_neg] (sources, then destinations), item t = j.  The pair is
+ *   uniform over the non-edge cells of the num_src x num_dst matrix.  exclude_self and ptr must be 0 / NULL.
+ *   1. T = num_src * num_dst - num_edges (must not overflow; sizes only); (-1, -1) if T <= 0.  R = the draw below T.
+ *   2. s = the smallest row of [0, num_src) with (s + 1) * num_dst - rowptr[s + 1] > R: a = 0, b = num_src; while a < b:
+ *      mid = (a + b) / 2; if (mid + 1) * num_dst - rowptr[mid + 1] > R then b = mid else a = mid + 1; s = a; (-1, -1) if
+ *      s == num_src.
+ *   3. r = R - (s * num_dst - rowptr[s]); (-1, -1) if row s is not valid or r lies outside [0, num_dst - (re - rs)).
+ *   4. (s, kth(row, 0, r)).
+ */
+PYG_HIP_API int pyg_hip_edge_lookup(int index_dtype, const void* rowptr, int64_t num_src, const void* col, int64_t num_edges,
+                                    const void* src, const void* dst, int64_t num_queries, void* out, void* stream);
+PYG_HIP_API int pyg_hip_negative_sample(int index_dtype, const void* rowptr, int64_t num_src, const void* col,
+                                        int64_t num_edges, const void* src, int64_t num_items, int64_t num_dst,
+                                        int64_t num_neg, uint64_t key, int exclude_self, const void* ptr, int64_t num_graphs,
+                                        void* out, void* stream);
 
 /*
  * Induced subgraph of a node list.  Replaces pyg::subgraph (schema pyg_lib/csrc/sampler/subgraph.cpp:30-32; CPU kernel

@@ -12,7 +12,7 @@ _HERE = osp.dirname(osp.abspath(__file__))
 _LIB = None
 
 OK = 0
-ABI_VERSION = 20  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
+ABI_VERSION = 21  # PYG_HIP_ABI_VERSION of the include/pyg_hip.h these bindings were written against
 DTYPES = {
     torch.float32: 0,
     torch.float64: 1,
@@ -210,6 +210,17 @@ def lib() -> ctypes.CDLL:
         L.pyg_hip_node2vec_walk.restype = c.c_int
         L.pyg_hip_node2vec_walk.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_int64,
                                             c.c_float, c.c_float, c.c_float, c.c_uint64, c.c_int, c.c_void_p, c.c_void_p]
+        # edge_lookup / negative_sample (include/pyg_hip.h, "Edge lookup and negative sampling"); src and ptr may be NULL
+        # (index_dtype, rowptr, num_src, col, num_edges, src, dst, num_queries, out, stream)
+        L.pyg_hip_edge_lookup.restype = c.c_int
+        L.pyg_hip_edge_lookup.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_int64,
+                                          c.c_void_p, c.c_void_p]
+        # (index_dtype, rowptr, num_src, col, num_edges, src, num_items, num_dst, num_neg, key, exclude_self, ptr, num_graphs,
+        #  out, stream)
+        L.pyg_hip_negative_sample.restype = c.c_int
+        L.pyg_hip_negative_sample.argtypes = [c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64, c.c_void_p, c.c_int64,
+                                              c.c_int64, c.c_int64, c.c_uint64, c.c_int, c.c_void_p, c.c_int64, c.c_void_p,
+                                              c.c_void_p]
         _LIB = L
     return _LIB
 

@@ -96,6 +96,16 @@ inline void* current_stream(const Tensor& t) {
   return static_cast<void*>(current_hip_stream((c10::DeviceIndex)t.get_device()));
 }
 
+// ---- the 64-bit key of a generator-seeded call (node2vec_walk, negative_sample) on the device ---------------------------
+// splitmix64's finaliser over the generator's (seed, offset): consecutive calls advance `offset` by 4, and without the mix
+// their keys -- hence their Philox streams -- would be neighbours
+inline uint64_t mix_key(uint64_t seed, uint64_t offset) {
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (offset + 1);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 // ---- the stream-bound allocator host of a pyg_hip_sampler_host (include/pyg_hip.h) -------------------------------------
 // `user` of the alloc / free callbacks: blocks come from the caching allocator on `stream`; an allocator exception is kept
 // in `error` (the C-ABI cannot carry it) and the library sees a null block.

@@ -77,15 +77,6 @@ Tensor node2vec_walk_keyed_cuda(const Tensor& rowptr, const Tensor& col, const T
   return out;
 }
 
-// splitmix64's finaliser over (seed, offset): consecutive calls advance `offset` by 4, and without the mix their keys --
-// hence their Philox streams -- would be neighbours
-uint64_t mix_key(uint64_t seed, uint64_t offset) {
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (offset + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 Tensor node2vec_walk_cuda(const Tensor& rowptr, const Tensor& col, const Tensor& seed, int64_t walk_length, double p,
                           double q) {
   TORCH_CHECK(seed.defined() && seed.is_cuda(), "'seed' must be a CUDA tensor");

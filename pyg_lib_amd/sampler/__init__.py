@@ -296,6 +296,83 @@ def node2vec_walk_keyed(
     return torch.ops.pyg.node2vec_walk_keyed(rowptr, col, seed, walk_length, p, q, key, max_attempts)
 
 
+def edge_lookup(rowptr: Tensor, col: Tensor, src: Tensor, dst: Tensor) -> Tensor:
+    r"""Where in :obj:`col` the edges ``(src[q], dst[q])`` of a CSR graph are (this build only).
+
+    ``out[q]`` is the position in :obj:`col` of the first entry of row ``src[q]`` that equals ``dst[q]`` (an edge id, if
+    edge ids are positions), found by binary search, or :obj:`-1` if there is none or ``src[q]`` is not a row of the
+    graph.  :obj:`col` must be ascending within each row.  All tensors are int32 or int64 vectors of one dtype on one
+    device; so is the result.  The same on a HIP device and on the CPU; capturable with ``torch.cuda.graph``.
+    """
+    return torch.ops.pyg.edge_lookup(rowptr, col, src, dst)
+
+
+def negative_sample(
+    rowptr: Tensor,
+    col: Tensor,
+    src: Optional[Tensor],
+    num_dst: int,
+    num_neg: int,
+    exclude_self: bool = False,
+    ptr: Optional[Tensor] = None,
+) -> Tensor:
+    r"""Exact uniform draws over the NON-edges of a CSR graph with :obj:`rowptr.numel() - 1` sources and :obj:`num_dst`
+    destinations (this build only).  No rejection loop: the r-th non-neighbour of a row is found directly by one binary
+    search, so every requested sample is returned, in bounded time, without a host read.
+
+    With :obj:`src` (the structured form) the result is ``[src.numel(), num_neg]``: ``out[i, j]`` is a destination ``x``
+    such that ``(src[i], x)`` is not an edge -- with :obj:`exclude_self` also ``x != src[i]``, with :obj:`ptr` (the node
+    offsets of a batch of graphs, ``G + 1`` entries) also in the same graph as ``src[i]`` -- uniform over all such ``x``,
+    drawn independently (with replacement), or :obj:`-1` where no such ``x`` exists or ``src[i]`` is not a row.
+    With ``src=None`` (the global form) the result is ``[2, num_neg]``, sources in row 0 and destinations in row 1: pairs
+    uniform over the non-edge cells of the whole matrix, ``(-1, -1)`` if it has none; :obj:`exclude_self` and :obj:`ptr`
+    are refused there.
+
+    How PyG's three compositions map onto this:
+
+    * ``structured_negative_sampling(edge_index, contains_neg_self_loops=c)``: ``src = edge_index[0]``, ``num_neg = 1``,
+      ``exclude_self = not c``; column 0 of the result is ``k``.
+    * ``batched_negative_sampling(edge_index, batch)``: the structured form plus ``ptr`` = the graphs' node offsets.
+    * ``negative_sampling(edge_index, num_nodes, num_neg_samples)``: ``src = None``, ``num_dst = num_nodes``.
+
+    :obj:`col` must be strictly ascending within each row (a coalesced graph); on other rows the results still lie in
+    range, but "is not an edge" and uniformity are not guaranteed.  One 64-bit key is drawn from the torch generator of
+    the tensors' device, so ``torch.manual_seed`` reproduces a call; the samples themselves are
+    :func:`negative_sample_keyed` with that key.  Cannot be captured into a graph (the key is drawn on the host): capture
+    the keyed form.
+
+    Args:
+        rowptr: Compressed source node indices.
+        col: Destination node indices, strictly ascending within each row.
+        src: The source of each row of the result, or :obj:`None` for the global form.
+        num_dst: The number of destination nodes.
+        num_neg: Samples per source (structured) or in all (global).
+        exclude_self: Never return ``src[i]`` itself (structured form only).
+        ptr: Node offsets of the graphs of a batch; negatives stay inside the source's graph (structured form only).
+    """
+    return torch.ops.pyg.negative_sample(rowptr, col, src, num_dst, num_neg, exclude_self, ptr)
+
+
+def negative_sample_keyed(
+    rowptr: Tensor,
+    col: Tensor,
+    src: Optional[Tensor],
+    num_dst: int,
+    num_neg: int,
+    key: int,
+    exclude_self: bool = False,
+    ptr: Optional[Tensor] = None,
+) -> Tensor:
+    r"""The deterministic core of :func:`negative_sample`: a pure function of its arguments, the same bit for bit on a HIP
+    device and on the CPU (DESIGN.md 2.18 is the specification).  Sample ``t`` (``i * num_neg + j`` in the structured
+    form, ``j`` in the global form) takes the first two words of ``at::Philox4_32(key, subsequence=t)`` as one 64-bit
+    word ``w`` and draws ``(w * n) >> 64`` among its ``n`` candidates; :obj:`key` is a signed 64-bit integer read as its
+    64 bits.  Integer arithmetic only.  Makes no host read and allocates only its output: capturable with
+    ``torch.cuda.graph``.
+    """
+    return torch.ops.pyg.negative_sample_keyed(rowptr, col, src, num_dst, num_neg, key, exclude_self, ptr)
+
+
 def release_table_cache() -> int:
     """Hands the node tables the sampler keeps between calls (up to 8 x 128 MiB per device) back to the caching allocator;
     returns how many are still in use by running calls.  ``torch.cuda.empty_cache()`` afterwards returns the memory to
@@ -326,4 +403,4 @@ def last_mode() -> str:
 
 __all__ = ['neighbor_sample', 'hetero_neighbor_sample', 'subgraph', 'random_walk', 'neighbor_sample_batched',
            'hetero_neighbor_sample_batched', 'release_table_cache', 'last_mode', 'rng_carry_stats', 'node2vec_walk',
-           'node2vec_walk_keyed']
+           'node2vec_walk_keyed', 'edge_lookup', 'negative_sample', 'negative_sample_keyed']
